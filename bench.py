@@ -7,7 +7,13 @@ configs[1]), on N GPUs of one node.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line (contract in the task statement).  Extra objects:
+Rank 0 prints ONE JSON line (contract in the task statement).  A plain run sets up, warms up, times the steps and prints
+the line; --dump-outputs DIR also writes what the last timed step computed (its weighted losses, the gradient norm and a
+seeded sample of the updated weights) as DIR/<name>.npy.  The backward accumulates with float atomics, so a trajectory of
+many steps drifts apart from run to run (the total loss after 60 steps moves by a few percent); with --dump-outputs the
+last timed step therefore starts again from the seeded initial training state (weights, Adam moments, step counters),
+which makes its inputs - weights, batch, random draws - the same in every run and its outputs agree to rounding.  The
+extra objects below take runs and steps of their own and are measured only with --full:
   roofline      achieved algorithmic GB/s of the dominant hand-written kernel (MSDA backward), measured with
                 HIP events around every launch inside the timed steps (same stream as the launches)
   cpu_baseline  the CPU oracle (oracle/step_ref.py, plain PyTorch fp32) timed on this host's cores on a bounded
@@ -16,8 +22,10 @@ Rank 0 prints ONE JSON line (contract in the task statement).  Extra objects:
                 the timed steps left behind, one 1024 x 1024 image, replayed random points) from the CPU oracle on identical
                 inputs, N=1 only; the oracle runs in the cpu_baseline child
   whole_step    algorithmic GFLOP/image x images/s against the composite matrix-core floor of the step
+                (arithmetic on the timed steps, so a plain run reports it too)
   categories    GPU time per step by kernel family (own HIP / library GEMM / MIOpen / ATen / copies), measured live with
                 torch.profiler's device activity records over extra steps after the timed region
+  frozen_backbone_encoder  the same benchmark with backbone + encoder frozen, in a child process
 """
 import argparse
 import json
@@ -321,6 +329,51 @@ def roofline_of(dom, kernels):
             "other_kernels": kernels}
 
 
+def training_state(step):
+    """(device tensors a training step reads and rewrites: flat fp32 weights, their bf16 copies, Adam moments; host counters:
+    optimizer step, iteration, LR-schedule position).  The model's buffers are not among them: nothing in the step updates one."""
+    return step._flat_state(), (step.optimizer.steps, step.iter, step.scheduler.last_iter)
+
+
+def snapshot_training_state(step):
+    tensors, host = training_state(step)
+    return [t.clone() for t in tensors], host
+
+
+def restore_training_state(step, snap):
+    """device-to-device copies on the launch stream and host counters: no host synchronisation"""
+    saved, (steps, it, last) = snap
+    for t, s in zip(training_state(step)[0], saved):
+        t.copy_(s, non_blocking=True)
+    step.optimizer.steps, step.iter, step.scheduler.last_iter = steps, it, last
+    step.scheduler._apply()
+
+
+def dump_outputs(d, step, losses, sample=3 << 20):
+    """what the last timed step handed its caller, as DIR/<name>.npy (float64 where the source is, float32 otherwise): every
+    weighted loss term, the global gradient norm, and a seeded sample of the flat weights after the update (all of them when
+    there are at most `sample`: 12 MiB in float32, 24 MiB at most)"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+
+    def save(name, t):
+        t = t.detach()
+        np.save(os.path.join(d, name + ".npy"), (t.double() if t.dtype == torch.float64 else t.float()).cpu().numpy())
+    for k, v in losses.items():
+        save(k, v)
+    save("grad_norm", step.optimizer.grad_norm())
+    groups = step.optimizer.flat.groups
+    total = sum(g.param.numel() for g in groups)
+    idx = torch.arange(total) if total <= sample else \
+        torch.randint(total, (sample,), generator=torch.Generator().manual_seed(0)).unique()      # sorted, fixed for a given model
+    params, lo = [], 0
+    for g in groups:
+        sel = (idx[(idx >= lo) & (idx < lo + g.param.numel())] - lo).to(g.param.device)
+        params.append(g.param[sel])
+        lo += g.param.numel()
+    save("params_sample", torch.cat(params))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -341,8 +394,17 @@ def main():
                     help="1: capture the whole step in a hipGraph (single GPU) and replay it, with ROCm's graph packet capture "
                          "switched off (packet-captured graphs go stale after eager launches on ROCm 7.2).  Off by default: "
                          "without packet capture a replay costs MORE host CPU than eager issue (DESIGN.md §5 'hipGraph')")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-launch kernel rooflines, the per-family GPU time table, "
+                         "the oracle parity step, the CPU baseline and the frozen backbone + encoder child (the --no-* / --skip-* "
+                         "options still switch single ones off)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (see dump_outputs); that "
+                         "step starts from the seeded initial training state, so the files are the same in every run")
     ap.add_argument("opts", nargs="*", help="extra KEY VALUE config overrides")
     a = ap.parse_args()
+    if not a.full:                                                 # a plain run: set up, warm up, time, (dump), print the line
+        a.no_cpu_baseline = a.no_categories = a.no_parity = a.skip_kernel_timing = True
 
     if a.cpu_baseline_only:
         print(json.dumps(cpu_baseline(list(a.opts), a.size, threads=a.cpu_threads or None, parity_file=a.parity_file or None)), flush=True)
@@ -383,6 +445,9 @@ def main():
     cfg = setup_cfg(os.path.join(ROOT, "partdistillation_amd", "configs", "proposal_learning", "r50_mask2former.yaml"), cfg_opts)
     torch.manual_seed(0)                                           # identical init on every rank (+ broadcast in TrainStep)
     step = TrainStep(cfg)
+    # --dump-outputs: the step's float atomics make a trajectory of many steps drift apart from run to run, so the last timed step
+    # restarts from the seeded initial state (one set of device copies inside the timed region) and its outputs are reproducible
+    init_state = snapshot_training_state(step) if a.dump_outputs else None
     batches = [make_batch(a.batch, a.size, seed=1234 + rank + 1000 * i, device="cuda") for i in range(4)]
 
     def barrier():
@@ -409,6 +474,8 @@ def main():
     c0 = time.process_time()
     marks[0].record()
     for i in range(a.steps):
+        if init_state is not None and i == a.steps - 1:
+            restore_training_state(step, init_state)
         losses = step(batches[i % len(batches)])
         marks[i + 1].record()
         if dbg:
@@ -418,6 +485,8 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(a.steps))
+    if a.dump_outputs and rank == 0:                               # before any --full step moves the weights on
+        dump_outputs(a.dump_outputs, step, losses)
     # per-launch timing of the hand-written MSDA kernels with HIP events on the launch stream.  Events cannot be
     # recorded between the nodes of a replayed graph, so these launches are timed in extra EAGER steps of the same
     # workload right after the timed region (when --graph 0 they are timed inside the timed region itself).
