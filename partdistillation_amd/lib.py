@@ -199,6 +199,12 @@ SIGNATURES = {
     "pd_mx8_gemm_supported": (_c_int, [_c_int] * 3),
     "pd_filter_transpose_table_bytes": (ctypes.c_int64, [_c_int]),
     "pd_filter_transpose_grouped": (_c_int, [_c_vp, _c_int, _c_vp, _c_vp, _c_vp]),
+    # include/pd_eval.h
+    "pd_eval_table_bytes": (ctypes.c_int64, [_c_int]),
+    "pd_eval_pack_grouped": (_c_int, [_c_vp, _c_int, _c_vp, _c_vp, _c_vp]),
+    "pd_eval_intersect_grouped": (_c_int, [_c_vp, _c_int, _c_vp, _c_vp, _c_vp]),
+    "pd_eval_confusion_grouped": (_c_int, [_c_vp, _c_int, _c_int, _c_vp, _c_int, _c_vp, _c_vp, _c_vp]),
+    "pd_eval_recall_grouped": (_c_int, [_c_vp, _c_int] + [_c_vp] * 6),
     "pd_cmd_fn_index": (_c_int, [ctypes.c_char_p]),
     "pd_cmd_fn_nargs": (_c_int, [_c_int]),
     "pd_cmd_replay": (_c_int, [_c_vp, _c_int, _c_vp, _c_int, _c_vp]),
