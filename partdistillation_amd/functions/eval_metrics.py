@@ -44,14 +44,15 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
-def _launch(fn, struct, fields, extra, device):
-    """fill a host descriptor list, stage it through a pinned ring slot and call fn(list, count, *extra, pinned, device table, stream)"""
+def _launch(fn, struct, fields, extra, device, table_bytes="pd_eval_table_bytes"):
+    """fill a host descriptor list, stage it through a pinned ring slot and call fn(list, count, *extra, pinned, device table, stream);
+    table_bytes names the library's size query of the kernel family (functions/pixel_grouping.py stages its tables here too)"""
     L = _lib.load()
     arr = (struct * len(fields))()
     for d, f in zip(arr, fields):
         for k, v in f.items():
             setattr(d, k, v)
-    nbytes = int(L.pd_eval_table_bytes(len(fields)))
+    nbytes = int(getattr(L, table_bytes)(len(fields)))
     cap = 1 << max(8, (nbytes - 1).bit_length())
     ring = _RINGS.get(cap)
     if ring is None:

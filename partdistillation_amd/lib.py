@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("PD_LIB_PATH") or os.path.join(_HERE, "libpd_hip.so") 
 CSRC = os.path.join(_HERE, "csrc")
 
 PD_F32, PD_F64, PD_BF16 = 0, 1, 2
-ABI_VERSION = 39
+ABI_VERSION = 40
 
 _c_int, _c_vp = ctypes.c_int, ctypes.c_void_p
 
@@ -205,6 +205,10 @@ SIGNATURES = {
     "pd_eval_intersect_grouped": (_c_int, [_c_vp, _c_int, _c_vp, _c_vp, _c_vp]),
     "pd_eval_confusion_grouped": (_c_int, [_c_vp, _c_int, _c_int, _c_vp, _c_int, _c_vp, _c_vp, _c_vp]),
     "pd_eval_recall_grouped": (_c_int, [_c_vp, _c_int] + [_c_vp] * 6),
+    # include/pd_grouping.h (evaluation twin: batched through a descriptor table)
+    "pd_grouping_table_bytes": (ctypes.c_int64, [_c_int]),
+    "pd_scores_argmax_resized_u8": (_c_int, [_c_vp, _c_int, _c_vp, _c_vp, _c_vp]),
+    "pd_masks_resize_u8": (_c_int, [_c_vp, _c_int, _c_vp, _c_vp, _c_vp]),
     "pd_cmd_fn_index": (_c_int, [ctypes.c_char_p]),
     "pd_cmd_fn_nargs": (_c_int, [_c_int]),
     "pd_cmd_replay": (_c_int, [_c_vp, _c_int, _c_vp, _c_int, _c_vp]),
