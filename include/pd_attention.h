@@ -16,7 +16,8 @@
  *   lse          : fp32 [B, H, Lq]   log-sum-exp of the scaled, masked scores (forward output, backward input)
  *   workspace    : fp32, at least pd_attn_workspace_floats(...) elements
  * Scores are q.k * scale.  A row whose keys are all blocked yields o = 0 and lse = -inf (the decoder un-blocks such
- * rows beforehand, reference :405).
+ * rows beforehand, reference :405); in the backward such a row (lse = -inf) gets dq = 0 and adds nothing to dk / dv.
+ * Lk = 0 is the same for every row (o = 0, lse = -inf, dq = 0); Lq = 0 gives dk = dv = 0.
  */
 #ifndef PD_ATTENTION_H
 #define PD_ATTENTION_H

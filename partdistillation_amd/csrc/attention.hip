@@ -834,10 +834,23 @@ extern "C" int pd_attn_bwd_d32_ld(const void *q, const void *k, const void *v, c
   if (ld_kv < H * D || (ld_kv & 3)) return pd_set_error(PD_ERR_INVALID_ARG, "pd_attn_bwd_d32_ld: ld_kv=%d (>= H * 32, a multiple of 4)", ld_kv);
   if (ld_kv != H * D && !(dtype == PD_BF16 && Lq <= MQ && !g_pd_dbg_attn_scalar))
     return pd_set_error(PD_ERR_INVALID_ARG, "pd_attn_bwd_d32_ld: strided k / v only on the matrix-core path (bf16, <= %d queries)", MQ);
-  if (B * Lq * Lk == 0) return PD_OK;
-  if (!o || !d_o || !lse || !dq || !dk || !dv || !workspace) return pd_set_error(PD_ERR_INVALID_ARG, "pd_attn_bwd_d32: null pointer");
   hipStream_t s = (hipStream_t)stream_;
+  if (B * Lq == 0) {                                  // no queries: dq is empty and no key or value receives a gradient (dk = dv = 0)
+    const size_t bytes = (size_t)B * Lk * H * D * (dtype == PD_BF16 ? 2 : 4);
+    if (bytes == 0) return PD_OK;
+    if (!dk || !dv) return pd_set_error(PD_ERR_INVALID_ARG, "pd_attn_bwd_d32: null pointer");
+    if (hipMemsetAsync(dk, 0, bytes, s) != hipSuccess || hipMemsetAsync(dv, 0, bytes, s) != hipSuccess)
+      return pd_set_error(PD_ERR_LAUNCH, "pd_attn_bwd_d32: clearing dk / dv failed");
+    return PD_OK;
+  }
   const int groups = B * H * Lq;
+  if (Lk == 0) {                                      // no keys: every row is a blocked row (o = 0, lse = -inf), dq = 0; dk / dv are empty
+    if (!dq) return pd_set_error(PD_ERR_INVALID_ARG, "pd_attn_bwd_d32: null pointer");
+    if (dtype == PD_BF16) hipLaunchKernelGGL(attn_bwd_dq_reduce<bf16_t>, dim3((groups + 7) / 8), dim3(256), 0, s, workspace, (bf16_t *)dq, B, H, Lq, 0);
+    else hipLaunchKernelGGL(attn_bwd_dq_reduce<float>, dim3((groups + 7) / 8), dim3(256), 0, s, workspace, (float *)dq, B, H, Lq, 0);
+    return pd_check_launch("pd_attn_bwd_d32");
+  }
+  if (!o || !d_o || !lse || !dq || !dk || !dv || !workspace) return pd_set_error(PD_ERR_INVALID_ARG, "pd_attn_bwd_d32: null pointer");
   if (dtype == PD_BF16 && Lq <= MQ && !g_pd_dbg_attn_scalar) {                     // matrix-core path
     const int kc = mfma_bwd_chunk(B, H, Lk), nc = nchunks(Lk, kc);
     if (mask) hipLaunchKernelGGL(attn_bwd_mfma<true>, dim3(nc, H, B), dim3(256), 0, s, (const bf16_t *)q, (const bf16_t *)k, (const bf16_t *)v,
