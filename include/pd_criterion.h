@@ -39,7 +39,11 @@ extern "C" {
  *   out_cols  int64   [nbatch, ncols_max]  selected col  (target) of pair k; entries k >= min(nrows, ncols[b]) are -1
  * The solver is the float64 shortest-augmenting-path algorithm SciPy uses
  * (Crouse 2016), including its tie-breaking scan order, so that the result is
- * SciPy's for the same matrix.  Limits: nrows <= 4096, ncols_max <= 64.
+ * SciPy's for the same matrix.  A problem that SciPy rejects (a NaN or -inf among its costs, or no finite
+ * assignment) keeps -1 in all its outputs; +inf costs are legal where a finite assignment exists.
+ * Limits: min(nrows, ncols_max) <= 64 and max(nrows, ncols_max) <= 4096, in either orientation; the largest
+ * shape needs ~120 KB of LDS per workgroup.  A shape beyond the limits, or beyond the device's per-workgroup
+ * LDS, returns PD_ERR_INVALID_ARG and launches nothing.
  */
 int pd_lsa_batched(const float *cost, const int32_t *ncols, int64_t *out_rows, int64_t *out_cols,
                    int nbatch, int nrows, int ncols_max, void *stream);

@@ -23,6 +23,27 @@ namespace {
 constexpr int kMaxSmall = 64;     // smaller dimension (rows of the solved problem)
 constexpr int kMaxLarge = 4096;   // larger dimension (columns of the solved problem)
 
+// Dynamic-LDS layout of one solved problem (R rows <= C columns), byte offsets: the kernel carves by it and the host
+// sizes the launch from it.  8-byte arrays first, then the ints, then the flags; v, dist, pred, row4col, todo and
+// col_seen have C entries, u, col4row and row_seen have R.
+struct Carve {
+  unsigned v, dist, u, pred, row4col, todo, col4row, row_seen, col_seen, bytes;
+  __host__ __device__ Carve(int R, int C)
+  {
+    const unsigned r = (unsigned)R, c = (unsigned)C;
+    v = 0;
+    dist = v + c * (unsigned)sizeof(double);
+    u = dist + c * (unsigned)sizeof(double);
+    pred = u + r * (unsigned)sizeof(double);
+    row4col = pred + c * (unsigned)sizeof(int);
+    todo = row4col + c * (unsigned)sizeof(int);
+    col4row = todo + c * (unsigned)sizeof(int);
+    row_seen = col4row + r * (unsigned)sizeof(int);
+    col_seen = row_seen + r;
+    bytes = col_seen + c;
+  }
+};
+
 struct Key {       // ordering of candidates inside one Dijkstra step
   double d;
   int unassigned;  // 1 if the column has no row yet
@@ -69,16 +90,16 @@ __global__ __launch_bounds__(64) void lsa_kernel(const float *__restrict__ cost_
   if (nc_in <= 0 || nrows <= 0) return;
   const bool tr = nc_in < nrows;            // SciPy transposes when there are more rows than columns
   const int R = tr ? nc_in : nrows, C = tr ? nrows : nc_in;
-  // LDS carve (C-sized arrays first, 8-byte ones first)
-  double *v = reinterpret_cast<double *>(smem);
-  double *dist = v + C;
-  double *u = dist + C;                      // R
-  int *pred = reinterpret_cast<int *>(u + R);
-  int *row4col = pred + C;
-  int *todo = row4col + C;
-  int *col4row = todo + C;                   // R
-  unsigned char *row_seen = reinterpret_cast<unsigned char *>(col4row + R);   // R
-  unsigned char *col_seen = row_seen + R;    // C
+  const Carve at(R, C);                      // R <= small, C <= large of the launch, so it fits what the host asked for
+  double *v = reinterpret_cast<double *>(smem + at.v);
+  double *dist = reinterpret_cast<double *>(smem + at.dist);
+  double *u = reinterpret_cast<double *>(smem + at.u);
+  int *pred = reinterpret_cast<int *>(smem + at.pred);
+  int *row4col = reinterpret_cast<int *>(smem + at.row4col);
+  int *todo = reinterpret_cast<int *>(smem + at.todo);
+  int *col4row = reinterpret_cast<int *>(smem + at.col4row);
+  unsigned char *row_seen = smem + at.row_seen;
+  unsigned char *col_seen = smem + at.col_seen;
   __shared__ int s_fail;
   for (int j = lane; j < C; j += 64) { v[j] = 0.0; row4col[j] = -1; }
   for (int i = lane; i < R; i += 64) { u[i] = 0.0; col4row[i] = -1; }
@@ -165,13 +186,31 @@ extern "C" int pd_lsa_batched(const float *cost, const int32_t *ncols, int64_t *
 {
   if (nbatch < 0 || nrows < 0 || ncols_max < 0) return pd_set_error(PD_ERR_INVALID_ARG, "pd_lsa_batched: negative size");
   if (nbatch == 0 || ncols_max == 0) return PD_OK;
-  if (!cost || !ncols || !out_rows || !out_cols) return pd_set_error(PD_ERR_INVALID_ARG, "pd_lsa_batched: null pointer");
+  if ((!cost && nrows > 0) || !ncols || !out_rows || !out_cols)   // nrows == 0: the cost tensor is empty and is never read
+    return pd_set_error(PD_ERR_INVALID_ARG, "pd_lsa_batched: null pointer");
   const int small = nrows < ncols_max ? nrows : ncols_max, large = nrows < ncols_max ? ncols_max : nrows;
   if (small > kMaxSmall || large > kMaxLarge)
     return pd_set_error(PD_ERR_INVALID_ARG, "pd_lsa_batched: problem %dx%d exceeds %dx%d", nrows, ncols_max, kMaxLarge, kMaxSmall);
-  const size_t C = (size_t)large, R = (size_t)(nrows > ncols_max ? nrows : ncols_max);   // upper bounds for both orientations
-  (void)R;
-  const size_t lds = (2 * C + C) * sizeof(double) + (3 * C + C) * sizeof(int) + 2 * C + 64;   // R <= C always
+  // every problem of the launch solves R <= small rows by C <= large columns, whichever way it is oriented
+  const size_t lds = Carve(small, large).bytes;
+  static int lds_limit = 0, lds_static = 0;      // per-workgroup LDS of the device; the kernel's static part (s_fail)
+  if (!lds_limit) {
+    int dev = 0, limit = 0;
+    hipFuncAttributes fa;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || limit <= 0) {
+      (void)hipGetLastError();
+      return pd_set_error(PD_ERR_LAUNCH, "pd_lsa_batched: cannot query the device's LDS per workgroup");
+    }
+    lds_static = hipFuncGetAttributes(&fa, (const void *)lsa_kernel) == hipSuccess ? (int)fa.sharedSizeBytes : (int)sizeof(int);
+    (void)hipGetLastError();
+    const size_t most = Carve(kMaxSmall, kMaxLarge).bytes, room = (size_t)(limit - lds_static);
+    (void)hipFuncSetAttribute((const void *)lsa_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(most < room ? most : room));
+    (void)hipGetLastError();
+    lds_limit = limit;
+  }
+  if (lds + (size_t)lds_static > (size_t)lds_limit)
+    return pd_set_error(PD_ERR_INVALID_ARG, "pd_lsa_batched: problem %dx%d needs %zu B of LDS, the device allows %d B per workgroup", nrows,
+                        ncols_max, lds + (size_t)lds_static, lds_limit);
   hipLaunchKernelGGL(lsa_kernel, dim3(nbatch), dim3(64), lds, (hipStream_t)stream_, cost, ncols, out_rows, out_cols, nrows,
                      ncols_max);
   return pd_check_launch("pd_lsa_batched");
