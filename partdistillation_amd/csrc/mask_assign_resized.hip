@@ -1,0 +1,498 @@
+// Per-pixel mask assignment at a resized output and its histogram (C-ABI in include/pd_assign.h): the evaluation branch of the supervised
+// model.  Both kernels serve a batch of images in one launch through a device table of entries, each with the index of its first
+// workgroup (wg_begin, ascending); a workgroup finds its entry by a scan of the (short) table.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "pd_common.h"
+#include "pd_assign.h"
+#include "pd_msda.h"                         // PD_OK / PD_ERR_*
+
+namespace {
+
+constexpr int kThreads = 256, kWaves = kThreads / 64;
+constexpr int kPx = 4;                       // pixels per lane of the assignment: 4 consecutive pixels of one output row
+constexpr int kTileW = 64 * kPx;             // columns per workgroup
+constexpr int kMixFloats = 1024;             // row-mixed logits a wavefront keeps in LDS: (k of one chunk) x (low-resolution columns under its 256 pixels)
+constexpr int kMinChunk = 8;                 // fewest k per chunk for which the LDS row mix is used; a wider column span is read from memory
+constexpr int kHistPx = 8;                   // consecutive pixels per thread and step of the histogram
+constexpr int kHistSteps = 4;                // steps per workgroup: 8192 pixels
+constexpr int kHistBins = 8192;              // int32 bins of a workgroup's LDS histogram
+
+template <typename E>
+__device__ __forceinline__ const E *find_entry(const E *table, int count, int64_t wg)
+{
+  int e = 0;
+  while (e + 1 < count && wg >= table[e + 1].wg_begin) ++e;
+  return pd_as_global(table + e);
+}
+
+// ATen's area_pixel_compute_source_index (align_corners = false) and the two taps of upsample_bilinear2d, every operation rounded on its
+// own: contraction is switched off inside tap_of (see csrc/pixel_grouping.hip)
+struct Tap {
+  int i0, i1;
+  float l0, l1;
+};
+
+__device__ __forceinline__ Tap tap_of(int dst, float scale, int in_size)
+{
+#pragma clang fp contract(off)
+  float src = scale * ((float)dst + 0.5f) - 0.5f;
+  src = src < 0.f ? 0.f : src;
+  Tap t;
+  t.i0 = (int)src;
+  t.i0 = t.i0 < in_size - 1 ? t.i0 : in_size - 1;
+  t.i1 = t.i0 + (t.i0 < in_size - 1 ? 1 : 0);
+  t.l1 = src - (float)t.i0;
+  t.l0 = 1.f - t.l1;
+  return t;
+}
+
+// the two chained interpolations along one axis: output index -> 4 low-resolution indices (i[0] the smallest, i[3] the largest) and weights
+struct Tap4 {
+  int i[4];
+  float w[4];
+};
+
+__device__ __forceinline__ Tap4 chain_of(int dst, float scale2, int crop, float scale1, int low)
+{
+  const Tap o = tap_of(dst, scale2, crop);
+  const Tap a = tap_of(o.i0, scale1, low), b = tap_of(o.i1, scale1, low);
+  Tap4 t;
+  t.i[0] = a.i0, t.i[1] = a.i1, t.i[2] = b.i0, t.i[3] = b.i1;
+  t.w[0] = o.l0 * a.l0, t.w[1] = o.l0 * a.l1, t.w[2] = o.l1 * b.l0, t.w[3] = o.l1 * b.l1;
+  return t;
+}
+
+// the source index of pd_mask_assign (csrc/grouping.hip), kept word for word: the identity case promises its bits
+__device__ __forceinline__ void src_index(int dst, float scale, int in_size, int &i0, int &ip, float &l0, float &l1)
+{
+  float src = scale * (dst + 0.5f) - 0.5f;
+  src = src < 0.f ? 0.f : src;
+  i0 = (int)src;
+  ip = (i0 < in_size - 1) ? 1 : 0;
+  l1 = src - i0;
+  l0 = 1.f - l1;
+}
+
+// ------------------------------------------------------------------------------------------------------------------- assignment
+// One wavefront per output row segment of 256 pixels.  K runs up to 256, so the row mix of pd_scores_argmax_resized_u8 (the 4
+// low-resolution rows of the output row combined once per (k, low column) into LDS) is walked in chunks of k that fit kMixFloats; the
+// per-pixel state (best product, its k, the largest v) lives in registers across the chunks.  A segment whose column span leaves fewer
+// than kMinChunk k per chunk (strong down-scaling) mixes per pixel from memory; the identity case evaluates pd_mask_assign's expression.
+// Segments without an object pixel have v_k = 0 for every k: they write the first arg-max of the scores and obj = 0.
+struct AssignEntry {
+  const float *logits;
+  const float *scores;
+  const uint8_t *object;
+  const int32_t *cls_of_query;
+  int16_t *arg;
+  uint8_t *obj;
+  int32_t *positive;
+  int16_t *cls;
+  int32_t K, h, w, Hi, Wi, H, W, tiles_x, identity, pad;
+  float sh1, sw1, sh2, sw2;
+  int64_t wg_begin;
+};
+
+__global__ void __launch_bounds__(kThreads) mask_assign_resized(const AssignEntry *table, int count)
+{
+  __shared__ float mix_s[kWaves][kMixFloats];
+  __shared__ int cnt[PD_ASSIGN_MAX_K];
+  const AssignEntry *e = find_entry(table, count, blockIdx.x);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int K = e->K, h = e->h, w = e->w, H = e->H, W = e->W;
+  for (int i = tid; i < K; i += kThreads) cnt[i] = 0;
+  const int64_t local = blockIdx.x - e->wg_begin;
+  const int tx = (int)(local % e->tiles_x), ty = (int)(local / e->tiles_x);
+  const int y = ty * kWaves + wave, xs = tx * kTileW, x0 = xs + lane * kPx;
+  const bool row_ok = y < H;
+  const float *logits = pd_as_global(e->logits);
+  const float *scores = pd_as_global(e->scores);
+  const uint8_t *object = pd_as_global(e->object);
+  const int32_t *cls_of_query = pd_as_global(e->cls_of_query);
+  int16_t *arg = pd_as_global(e->arg);
+  uint8_t *obj = pd_as_global(e->obj);
+  int32_t *positive = pd_as_global(e->positive);
+  int16_t *cls = pd_as_global(e->cls);
+  const int64_t o = (int64_t)y * W + x0;
+  const int hw = h * w;
+
+  bool in[kPx];
+  float om[kPx];
+#pragma unroll
+  for (int j = 0; j < kPx; ++j) {
+    in[j] = row_ok && x0 + j < W;
+    om[j] = (in[j] && (!object || object[o + j])) ? 1.f : 0.f;
+  }
+  const bool any = __ballot(om[0] + om[1] + om[2] + om[3] != 0.f) != 0;        // wave-uniform: this segment has pixels that see the logits
+
+  // the column span of the workgroup's 256 pixels is the same for its 4 rows: the chunk loop below is uniform over the workgroup
+  const int xe = (xs + kTileW < W ? xs + kTileW : W) - 1;
+  const int cmin = chain_of(xs, e->sw2, e->Wi, e->sw1, w).i[0];
+  const int ncols = chain_of(xe, e->sw2, e->Wi, e->sw1, w).i[3] - cmin + 1;
+  const bool identity = e->identity != 0;
+  const bool use_lds = !identity && ncols * kMinChunk <= kMixFloats;
+  const int kc = use_lds ? (kMixFloats / ncols < K ? kMixFloats / ncols : K) : K;
+
+  float best[kPx], vmax[kPx];
+  int besti[kPx];
+#pragma unroll
+  for (int j = 0; j < kPx; ++j) best[j] = -INFINITY, vmax[j] = -INFINITY, besti[j] = 0;
+
+  // one k for the lane's 4 pixels: positive-pixel ballot, product with the score, running maxima
+  auto consume = [&](int k, const float (&v)[kPx]) {
+    int c = 0;
+#pragma unroll
+    for (int j = 0; j < kPx; ++j) c += __popcll(__ballot(in[j] && v[j] > 0.f));
+    if (lane == 0 && c) atomicAdd(&cnt[k], c);
+    const float s = scores[k];
+#pragma unroll
+    for (int j = 0; j < kPx; ++j) {
+      const float p = s * (1.f / (1.f + __expf(-v[j])));
+      if (p > best[j]) {
+        best[j] = p;
+        besti[j] = k;
+      }
+      vmax[j] = fmaxf(vmax[j], v[j]);
+    }
+  };
+
+  __syncthreads();                                                             // cnt is zero
+  if (identity) {
+    if (any) {
+      int y0 = 0, yp = 0, c0[kPx], cp[kPx];
+      float hy0 = 0.f, hy1 = 0.f, wx0[kPx], wx1[kPx];
+      src_index(y, e->sh1, h, y0, yp, hy0, hy1);
+#pragma unroll
+      for (int j = 0; j < kPx; ++j) {
+        c0[j] = cp[j] = 0, wx0[j] = wx1[j] = 0.f;
+        if (in[j]) src_index(x0 + j, e->sw1, w, c0[j], cp[j], wx0[j], wx1[j]);
+      }
+      for (int k = 0; k < K; ++k) {
+        const float *s = logits + k * hw;
+        float v[kPx];
+#pragma unroll
+        for (int j = 0; j < kPx; ++j) {
+          v[j] = 0.f;
+          if (in[j]) {
+            const int a = y0 * w + c0[j], b = a + cp[j], c = (y0 + yp) * w + c0[j], d = c + cp[j];
+            v[j] = (hy0 * (wx0[j] * s[a] + wx1[j] * s[b]) + hy1 * (wx0[j] * s[c] + wx1[j] * s[d])) * om[j];
+          }
+        }
+        consume(k, v);
+      }
+    }
+  } else {
+    Tap4 ry, cx[kPx];
+    if (any) {
+      ry = chain_of(y, e->sh2, e->Hi, e->sh1, h);
+#pragma unroll
+      for (int j = 0; j < kPx; ++j) cx[j] = chain_of(x0 + j < W ? x0 + j : W - 1, e->sw2, e->Wi, e->sw1, w);
+    }
+    auto rowmix = [&](int k, int c) {
+      const float *s = logits + k * hw + c;
+      return (ry.w[0] * s[ry.i[0] * w] + ry.w[1] * s[ry.i[1] * w]) + (ry.w[2] * s[ry.i[2] * w] + ry.w[3] * s[ry.i[3] * w]);
+    };
+    if (use_lds) {
+      float *mix = mix_s[wave];
+      for (int k0 = 0; k0 < K; k0 += kc) {
+        const int kn = K - k0 < kc ? K - k0 : kc;
+        if (any)
+          for (int idx = lane; idx < kn * ncols; idx += 64) {
+            const int k = idx / ncols, c = idx - k * ncols;
+            mix[idx] = rowmix(k0 + k, cmin + c);
+          }
+        __syncthreads();
+        if (any)
+          for (int k = 0; k < kn; ++k) {
+            const int b = k * ncols - cmin;
+            float v[kPx];
+#pragma unroll
+            for (int j = 0; j < kPx; ++j)
+              v[j] = ((cx[j].w[0] * mix[b + cx[j].i[0]] + cx[j].w[1] * mix[b + cx[j].i[1]]) +
+                      (cx[j].w[2] * mix[b + cx[j].i[2]] + cx[j].w[3] * mix[b + cx[j].i[3]])) * om[j];
+            consume(k0 + k, v);
+          }
+        __syncthreads();
+      }
+    } else if (any) {
+      for (int k = 0; k < K; ++k) {
+        float v[kPx];
+#pragma unroll
+        for (int j = 0; j < kPx; ++j) {
+          v[j] = 0.f;
+          if (in[j])
+            v[j] = ((cx[j].w[0] * rowmix(k, cx[j].i[0]) + cx[j].w[1] * rowmix(k, cx[j].i[1])) +
+                    (cx[j].w[2] * rowmix(k, cx[j].i[2]) + cx[j].w[3] * rowmix(k, cx[j].i[3]))) * om[j];
+        }
+        consume(k, v);
+      }
+    }
+  }
+  if (!any) {                                                                  // v_k = 0 everywhere: sigmoid = 0.5, the first largest score wins
+    float b = -INFINITY;
+    int bi = 0;
+    for (int k = 0; k < K; ++k) {
+      const float p = scores[k] * 0.5f;
+      if (p > b) b = p, bi = k;
+    }
+#pragma unroll
+    for (int j = 0; j < kPx; ++j) besti[j] = bi;
+  }
+
+  if (in[0]) {
+    uint8_t ob[kPx];
+    int16_t cl[kPx];
+#pragma unroll
+    for (int j = 0; j < kPx; ++j) {
+      ob[j] = vmax[j] > 0.f ? 1 : 0;
+      cl[j] = -1;
+    }
+    if (cls_of_query && cls) {
+#pragma unroll
+      for (int j = 0; j < kPx; ++j)
+        if (in[j] && ob[j]) cl[j] = (int16_t)cls_of_query[besti[j]];
+    }
+    int16_t *ap = arg + o;
+    uint8_t *op = obj + o;
+    const bool full = in[kPx - 1];
+    if (full && ((uintptr_t)ap & 7) == 0) {
+      uint2 v;
+      v.x = (uint32_t)(uint16_t)besti[0] | ((uint32_t)(uint16_t)besti[1] << 16);
+      v.y = (uint32_t)(uint16_t)besti[2] | ((uint32_t)(uint16_t)besti[3] << 16);
+      *reinterpret_cast<uint2 *>(ap) = v;
+    } else {
+#pragma unroll
+      for (int j = 0; j < kPx; ++j)
+        if (in[j]) ap[j] = (int16_t)besti[j];
+    }
+    if (full && ((uintptr_t)op & 3) == 0) {
+      *reinterpret_cast<uint32_t *>(op) = (uint32_t)ob[0] | ((uint32_t)ob[1] << 8) | ((uint32_t)ob[2] << 16) | ((uint32_t)ob[3] << 24);
+    } else {
+#pragma unroll
+      for (int j = 0; j < kPx; ++j)
+        if (in[j]) op[j] = ob[j];
+    }
+    if (cls) {
+      int16_t *cp = cls + o;
+      if (full && ((uintptr_t)cp & 7) == 0) {
+        uint2 v;
+        v.x = (uint32_t)(uint16_t)cl[0] | ((uint32_t)(uint16_t)cl[1] << 16);
+        v.y = (uint32_t)(uint16_t)cl[2] | ((uint32_t)(uint16_t)cl[3] << 16);
+        *reinterpret_cast<uint2 *>(cp) = v;
+      } else {
+#pragma unroll
+        for (int j = 0; j < kPx; ++j)
+          if (in[j]) cp[j] = cl[j];
+      }
+    }
+  }
+  __syncthreads();
+  for (int k = tid; k < K; k += kThreads)
+    if (cnt[k]) atomicAdd(positive + k, cnt[k]);
+}
+
+// ------------------------------------------------------------------------------------------------------------------- histogram
+// A workgroup owns 8192 consecutive pixels; a thread reads 8 consecutive pixels per step (one 16-byte load of keys, 8-byte loads of the
+// object map and of each ground-truth mask) and adds RUNS of equal keys to the LDS bins (assignment maps are piecewise constant, so one
+// atomic per pixel would serialise on a few addresses).  Bins of a pass: won[n], area[n], inter[n][Gc], gt_area[Gc]; when n * (G + 2) + G
+// exceeds kHistBins the ground-truth masks are walked in passes of Gc.  Non-zero bins reach memory by one 64-bit atomic each.
+struct HistEntry {
+  const int16_t *key;
+  const uint8_t *obj;
+  const uint8_t *gt;
+  int64_t *won, *area, *inter, *gt_area;
+  int32_t n, G;
+  int64_t hw;
+  int64_t wg_begin;
+};
+
+__device__ __forceinline__ uint64_t load_bytes8(const uint8_t *p, int cnt)
+{
+  if (cnt == kHistPx && ((uintptr_t)p & 7) == 0) return *reinterpret_cast<const uint64_t *>(p);
+  uint64_t v = 0;
+#pragma unroll
+  for (int j = 0; j < kHistPx; ++j)
+    if (j < cnt) v |= (uint64_t)p[j] << (8 * j);
+  return v;
+}
+
+// 0x80 in every non-zero byte
+__device__ __forceinline__ uint64_t nonzero_bytes(uint64_t m)
+{
+  const uint64_t lo = 0x7f7f7f7f7f7f7f7full;
+  return (((m & lo) + lo) | m) & ~lo;
+}
+
+__device__ __forceinline__ void add64(int64_t *p, int v) { atomicAdd(reinterpret_cast<unsigned long long *>(p), (unsigned long long)v); }
+
+__global__ void __launch_bounds__(kThreads) assign_histogram(const HistEntry *table, int count)
+{
+  __shared__ int bins[kHistBins];
+  const HistEntry *e = find_entry(table, count, blockIdx.x);
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int n = e->n, G = e->G;
+  const int64_t hw = e->hw;
+  const int16_t *key = pd_as_global(e->key);
+  const uint8_t *obj = pd_as_global(e->obj);
+  const uint8_t *gt = pd_as_global(e->gt);
+  int64_t *won = pd_as_global(e->won), *area = pd_as_global(e->area), *inter = pd_as_global(e->inter), *gt_area = pd_as_global(e->gt_area);
+  const int64_t base = (blockIdx.x - e->wg_begin) * (int64_t)(kThreads * kHistPx * kHistSteps);
+  int Gc = (kHistBins - 2 * n) / (n + 1);
+  Gc = Gc < G ? Gc : G;
+  for (int g0 = 0; g0 == 0 || g0 < G; g0 += Gc) {                             // (G == 0: one pass for won and area)
+    const int gn = G - g0 < Gc ? G - g0 : Gc;
+    const int total = 2 * n + n * gn + gn;
+    for (int i = tid; i < total; i += kThreads) bins[i] = 0;
+    __syncthreads();
+    for (int step = 0; step < kHistSteps; ++step) {
+      const int64_t p = base + ((int64_t)step * kThreads + tid) * kHistPx;
+      const int64_t left = hw - p;
+      const int c = left >= kHistPx ? kHistPx : (left > 0 ? (int)left : 0);
+      int k[kHistPx];
+      uint64_t ok = 0;                                                         // 0x80 in the bytes of pixels with a key in [0, n) and obj set
+      if (c > 0) {
+        const int16_t *kp = key + p;
+        if (c == kHistPx && ((uintptr_t)kp & 15) == 0) {
+          const uint4 v = *reinterpret_cast<const uint4 *>(kp);
+          k[0] = (int16_t)(v.x & 0xffff), k[1] = (int16_t)(v.x >> 16), k[2] = (int16_t)(v.y & 0xffff), k[3] = (int16_t)(v.y >> 16);
+          k[4] = (int16_t)(v.z & 0xffff), k[5] = (int16_t)(v.z >> 16), k[6] = (int16_t)(v.w & 0xffff), k[7] = (int16_t)(v.w >> 16);
+        } else {
+#pragma unroll
+          for (int j = 0; j < kHistPx; ++j) k[j] = j < c ? (int)kp[j] : -1;
+        }
+        const uint64_t ob = nonzero_bytes(load_bytes8(obj + p, c));
+#pragma unroll
+        for (int j = 0; j < kHistPx; ++j) {
+          if (k[j] < 0 || k[j] >= n) k[j] = -1;
+          if (k[j] >= 0) ok |= ob & (0x80ull << (8 * j));
+        }
+        if (g0 == 0) {                                                         // won and area: runs of equal keys
+          int cur = -1, cw = 0, ca = 0;
+#pragma unroll
+          for (int j = 0; j < kHistPx; ++j) {
+            if (k[j] != cur) {
+              if (cur >= 0) {
+                atomicAdd(&bins[cur], cw);
+                if (ca) atomicAdd(&bins[n + cur], ca);
+              }
+              cur = k[j], cw = 0, ca = 0;
+            }
+            cw += 1;
+            ca += (int)((ok >> (8 * j + 7)) & 1);
+          }
+          if (cur >= 0) {
+            atomicAdd(&bins[cur], cw);
+            if (ca) atomicAdd(&bins[n + cur], ca);
+          }
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < kHistPx; ++j) k[j] = -1;
+      }
+      for (int jj = 0; jj < gn; ++jj) {
+        uint64_t m = 0;
+        if (c > 0) m = nonzero_bytes(load_bytes8(gt + (int64_t)(g0 + jj) * hw + p, c));
+        int ga = __popcll(m);
+        for (int off = 32; off > 0; off >>= 1) ga += __shfl_xor(ga, off);
+        if (lane == 0 && ga) atomicAdd(&bins[2 * n + n * gn + jj], ga);
+        m &= ok;
+        if (m) {
+          int cur = -1, ci = 0;
+#pragma unroll
+          for (int j = 0; j < kHistPx; ++j) {
+            const int t = (int)((m >> (8 * j + 7)) & 1);
+            const int kk = t ? k[j] : -1;
+            if (kk != cur) {
+              if (cur >= 0) atomicAdd(&bins[2 * n + cur * gn + jj], ci);
+              cur = kk, ci = 0;
+            }
+            ci += 1;
+          }
+          if (cur >= 0) atomicAdd(&bins[2 * n + cur * gn + jj], ci);
+        }
+      }
+    }
+    __syncthreads();
+    for (int i = tid; i < total; i += kThreads) {
+      const int v = bins[i];
+      if (!v) continue;
+      if (i < n) add64(won + i, v);
+      else if (i < 2 * n) add64(area + (i - n), v);
+      else if (i < 2 * n + n * gn) {
+        const int r = i - 2 * n, kk = r / gn, jj = r - kk * gn;
+        add64(inter + (int64_t)kk * G + g0 + jj, v);
+      } else add64(gt_area + g0 + (i - 2 * n - n * gn), v);
+    }
+    __syncthreads();
+    if (Gc <= 0) break;
+  }
+}
+
+int upload(const void *h, size_t bytes, void *table_device, hipStream_t st, const char *what)
+{
+  if (hipMemcpyAsync(table_device, h, bytes, hipMemcpyHostToDevice, st) != hipSuccess)
+    return pd_set_error(PD_ERR_LAUNCH, "%s: table upload failed", what);
+  return PD_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t pd_assign_table_bytes(int32_t count)
+{
+  const size_t m = sizeof(AssignEntry) > sizeof(HistEntry) ? sizeof(AssignEntry) : sizeof(HistEntry);
+  return (int64_t)(count > 0 ? count : 0) * (int64_t)m;
+}
+
+extern "C" int pd_mask_assign_resized(const PdAssignResized *list, int32_t count, void *table_host_pinned, void *table_device, void *stream)
+{
+  if (count <= 0) return PD_OK;
+  if (!list || !table_host_pinned || !table_device) return pd_set_error(PD_ERR_INVALID_ARG, "pd_mask_assign_resized: null pointer");
+  AssignEntry *hst = reinterpret_cast<AssignEntry *>(table_host_pinned);
+  int64_t wgs = 0;
+  for (int i = 0; i < count; ++i) {
+    const PdAssignResized &d = list[i];
+    if (d.K < 1 || d.K > PD_ASSIGN_MAX_K || d.h <= 0 || d.w <= 0 || d.Hp <= 0 || d.Wp <= 0 || d.Hi <= 0 || d.Wi <= 0 || d.Hi > d.Hp ||
+        d.Wi > d.Wp || d.H <= 0 || d.W <= 0 || (int64_t)d.K * d.h * d.w >= INT32_MAX || !d.logits || !d.scores || !d.arg || !d.obj ||
+        !d.positive)
+      return pd_set_error(PD_ERR_INVALID_ARG,
+                          "pd_mask_assign_resized: image %d: K=%d h=%d w=%d Hp=%d Wp=%d Hi=%d Wi=%d H=%d W=%d (1 <= K <= %d, Hi <= Hp, "
+                          "Wi <= Wp, non-null logits / scores / arg / obj / positive required)",
+                          i, d.K, d.h, d.w, d.Hp, d.Wp, d.Hi, d.Wi, d.H, d.W, PD_ASSIGN_MAX_K);
+    const int32_t tiles_x = (d.W + kTileW - 1) / kTileW, tiles_y = (d.H + kWaves - 1) / kWaves;
+    hst[i] = AssignEntry{d.logits, d.scores, d.object, d.cls_of_query, d.arg, d.obj, d.positive, d.cls, d.K, d.h, d.w, d.Hi, d.Wi, d.H, d.W,
+                         tiles_x, (d.H == d.Hi && d.W == d.Wi) ? 1 : 0, 0,
+                         (float)d.h / (float)d.Hp, (float)d.w / (float)d.Wp, (float)d.Hi / (float)d.H, (float)d.Wi / (float)d.W, wgs};
+    wgs += (int64_t)tiles_x * tiles_y;
+  }
+  if (wgs >= INT32_MAX) return pd_set_error(PD_ERR_INVALID_ARG, "pd_mask_assign_resized: %lld workgroups", (long long)wgs);
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = upload(hst, (size_t)count * sizeof(AssignEntry), table_device, st, "pd_mask_assign_resized")) return rc;
+  hipLaunchKernelGGL(mask_assign_resized, dim3((unsigned)wgs), dim3(kThreads), 0, st, (const AssignEntry *)table_device, count);
+  return pd_check_launch("pd_mask_assign_resized");
+}
+
+extern "C" int pd_assign_histogram(const PdAssignHistogram *list, int32_t count, void *table_host_pinned, void *table_device, void *stream)
+{
+  if (count <= 0) return PD_OK;
+  if (!list || !table_host_pinned || !table_device) return pd_set_error(PD_ERR_INVALID_ARG, "pd_assign_histogram: null pointer");
+  HistEntry *hst = reinterpret_cast<HistEntry *>(table_host_pinned);
+  int64_t wgs = 0;
+  const int64_t per_wg = (int64_t)kThreads * kHistPx * kHistSteps;
+  for (int i = 0; i < count; ++i) {
+    const PdAssignHistogram &d = list[i];
+    if (d.n < 1 || d.n > PD_ASSIGN_MAX_KEYS || d.G < 0 || d.G > PD_ASSIGN_MAX_GT || d.hw <= 0 || !d.key || !d.obj || !d.won || !d.area ||
+        (d.G > 0 && (!d.gt || !d.inter || !d.gt_area)))
+      return pd_set_error(PD_ERR_INVALID_ARG,
+                          "pd_assign_histogram: image %d: n=%d G=%d hw=%lld (1 <= n <= %d, 0 <= G <= %d, hw > 0, non-null pointers required)", i,
+                          d.n, d.G, (long long)d.hw, PD_ASSIGN_MAX_KEYS, PD_ASSIGN_MAX_GT);
+    hst[i] = HistEntry{d.key, d.obj, d.gt, d.won, d.area, d.inter, d.gt_area, d.n, d.G, d.hw, wgs};
+    wgs += (d.hw + per_wg - 1) / per_wg;
+  }
+  if (wgs >= INT32_MAX) return pd_set_error(PD_ERR_INVALID_ARG, "pd_assign_histogram: %lld workgroups", (long long)wgs);
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = upload(hst, (size_t)count * sizeof(HistEntry), table_device, st, "pd_assign_histogram")) return rc;
+  hipLaunchKernelGGL(assign_histogram, dim3((unsigned)wgs), dim3(kThreads), 0, st, (const HistEntry *)table_device, count);
+  return pd_check_launch("pd_assign_histogram");
+}

@@ -4,6 +4,7 @@
 - proposal_metrics: AR@k of proposal_evaluator.py:_evaluate_box_proposals / _eval_proposals (recall per threshold and its mean in
   float32, as the reference computes them from its float32 overlap vector).
 - measure_miou / miou_metrics: miou_evaluator.py:measure_mIOU and the C-* / A-* aggregation of its evaluate(), in float64.
+- supervised_miou_metrics: supervised_miou_evaluator.py:evaluate (one table, no object classes).
 - majority_voting: miou_matcher.py:majority_voting (first index on ties)."""
 import logging
 
@@ -72,6 +73,14 @@ def measure_miou(conf, class_names, num_classes):
         res["mACC"] = 100 * (np.sum(acc[has_gt]) / np.sum(has_gt))
         res["pACC"] = 100 * (np.sum(tp) / np.sum(pos_gt))
     return res
+
+
+def supervised_miou_metrics(conf, class_names, num_classes):
+    """supervised_miou_evaluator.py:evaluate on one confusion matrix [(n + 1), (n + 1)]: mIoU is the mean of the per-class IoUs that
+    are not NaN (classes with ground-truth pixels), mACC / mIoPred those of measure_mIOU (the same formulas as measure_miou)"""
+    r = measure_miou(conf, class_names, num_classes)
+    ious = [v for k, v in r.items() if "IoU-" in k and not np.isnan(v)]
+    return {"mIoU": np.mean(ious) if ious else np.nan, "mACC": r["mACC"], "mIoPred": r["mIoPred"]}
 
 
 def seen_slots(conf):

@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("PD_LIB_PATH") or os.path.join(_HERE, "libpd_hip.so") 
 CSRC = os.path.join(_HERE, "csrc")
 
 PD_F32, PD_F64, PD_BF16 = 0, 1, 2
-ABI_VERSION = 40
+ABI_VERSION = 41
 
 _c_int, _c_vp = ctypes.c_int, ctypes.c_void_p
 
@@ -209,6 +209,10 @@ SIGNATURES = {
     "pd_grouping_table_bytes": (ctypes.c_int64, [_c_int]),
     "pd_scores_argmax_resized_u8": (_c_int, [_c_vp, _c_int, _c_vp, _c_vp, _c_vp]),
     "pd_masks_resize_u8": (_c_int, [_c_vp, _c_int, _c_vp, _c_vp, _c_vp]),
+    # include/pd_assign.h
+    "pd_assign_table_bytes": (ctypes.c_int64, [_c_int]),
+    "pd_mask_assign_resized": (_c_int, [_c_vp, _c_int, _c_vp, _c_vp, _c_vp]),
+    "pd_assign_histogram": (_c_int, [_c_vp, _c_int, _c_vp, _c_vp, _c_vp]),
     "pd_cmd_fn_index": (_c_int, [ctypes.c_char_p]),
     "pd_cmd_fn_nargs": (_c_int, [_c_int]),
     "pd_cmd_replay": (_c_int, [_c_vp, _c_int, _c_vp, _c_int, _c_vp]),
