@@ -2,13 +2,13 @@
 // greedy cover of the box-proposal recall — every count an exact integer, a batch of images one launch per kernel.
 //
 // Workgroup -> work item: every grouped kernel gets a device table of entries, each with the index of its first workgroup
-// (wg_begin, ascending); a workgroup finds its entry by a scan of the (short) table.
+// (wg_begin, ascending); a workgroup finds its entry by a scan of the (short) table (grouped_table.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "pd_common.h"
-#include "pd_msda.h"
 #include "pd_eval.h"
+#include "grouped_table.h"
 
 namespace {
 
@@ -19,14 +19,6 @@ __device__ __forceinline__ uint64_t readlane64(uint64_t v, int k)
   const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, k);
   const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), k);
   return ((uint64_t)hi << 32) | lo;
-}
-
-template <typename E>
-__device__ __forceinline__ const E *find_entry(const E *table, int count, int64_t wg)
-{
-  int e = 0;
-  while (e + 1 < count && wg >= table[e + 1].wg_begin) ++e;
-  return pd_as_global(table + e);
 }
 
 // ------------------------------------------------------------------------------------------------------------------- bit planes
@@ -369,14 +361,6 @@ __global__ void __launch_bounds__(kRecallThreads) eval_recall(const RecallEntry 
   }
 }
 
-template <typename E>
-int upload(const E *h, int count, void *table_device, hipStream_t st, const char *what)
-{
-  if (hipMemcpyAsync(table_device, h, (size_t)count * sizeof(E), hipMemcpyHostToDevice, st) != hipSuccess)
-    return pd_set_error(PD_ERR_LAUNCH, "%s: table upload failed", what);
-  return PD_OK;
-}
-
 }  // namespace
 
 extern "C" int64_t pd_eval_table_bytes(int32_t count)
@@ -390,47 +374,39 @@ extern "C" int64_t pd_eval_table_bytes(int32_t count)
 
 extern "C" int pd_eval_pack_grouped(const PdEvalMaskSet *list, int32_t count, void *table_host_pinned, void *table_device, void *stream)
 {
-  if (count <= 0) return PD_OK;
-  if (!list || !table_host_pinned || !table_device) return pd_set_error(PD_ERR_INVALID_ARG, "pd_eval_pack_grouped: null pointer");
-  PackEntry *h = reinterpret_cast<PackEntry *>(table_host_pinned);
-  int64_t wgs = 0;
-  for (int i = 0; i < count; ++i) {
-    const PdEvalMaskSet &d = list[i];
-    if (d.n < 0 || d.hw <= 0 || d.hw >= (int64_t)1 << 32 || (d.n > 0 && (!d.masks || !d.bits || !d.area)))
-      return pd_set_error(PD_ERR_INVALID_ARG, "pd_eval_pack_grouped: set %d: n >= 0, 0 < hw < 2^32 and non-null pointers required", i);
-    const int64_t words = (d.hw + 63) / 64;
-    const int64_t chunks = (words * 4 + kPackPiecesPerWg - 1) / kPackPiecesPerWg;
-    const int aligned = (d.hw % 16 == 0) && (((uintptr_t)d.masks & 15) == 0);
-    h[i] = PackEntry{d.masks, d.bits, d.area, d.hw, words, (int32_t)chunks, aligned, wgs};
-    wgs += chunks * d.n;
-  }
-  if (wgs == 0) return PD_OK;
-  if (wgs >= INT32_MAX) return pd_set_error(PD_ERR_INVALID_ARG, "pd_eval_pack_grouped: %lld workgroups", (long long)wgs);
   hipStream_t st = (hipStream_t)stream;
-  if (int rc = upload(h, count, table_device, st, "pd_eval_pack_grouped")) return rc;
+  const int64_t wgs = stage_table<PackEntry>(
+      "pd_eval_pack_grouped", list, count, true, table_host_pinned, table_device, st,
+      [](const PdEvalMaskSet &d, int i, PackEntry &e, int64_t wg_begin) -> int64_t {
+        if (d.n < 0 || d.hw <= 0 || d.hw >= (int64_t)1 << 32 || (d.n > 0 && (!d.masks || !d.bits || !d.area)))
+          return pd_set_error(PD_ERR_INVALID_ARG, "pd_eval_pack_grouped: set %d: n >= 0, 0 < hw < 2^32 and non-null pointers required", i);
+        const int64_t words = (d.hw + 63) / 64;
+        const int64_t chunks = (words * 4 + kPackPiecesPerWg - 1) / kPackPiecesPerWg;
+        const int aligned = (d.hw % 16 == 0) && (((uintptr_t)d.masks & 15) == 0);
+        e = PackEntry{d.masks, d.bits, d.area, d.hw, words, (int32_t)chunks, aligned, wg_begin};
+        return chunks * d.n;
+      });
+  if (wgs <= 0) return (int)wgs;
   hipLaunchKernelGGL(eval_pack, dim3((unsigned)wgs), dim3(kThreads), 0, st, (const PackEntry *)table_device, count);
   return pd_check_launch("pd_eval_pack_grouped");
 }
 
 extern "C" int pd_eval_intersect_grouped(const PdEvalPairs *list, int32_t count, void *table_host_pinned, void *table_device, void *stream)
 {
-  if (count <= 0) return PD_OK;
-  if (!list || !table_host_pinned || !table_device) return pd_set_error(PD_ERR_INVALID_ARG, "pd_eval_intersect_grouped: null pointer");
-  PairsEntry *h = reinterpret_cast<PairsEntry *>(table_host_pinned);
-  int64_t wgs = 0;
-  for (int i = 0; i < count; ++i) {
-    const PdEvalPairs &d = list[i];
-    if (d.p < 1 || d.g < 1 || d.g > PD_EVAL_MAX_GT || d.words < 1 || !d.a || !d.b || !d.inter)
-      return pd_set_error(PD_ERR_INVALID_ARG, "pd_eval_intersect_grouped: pair %d: p >= 1, 1 <= g <= %d, words >= 1, non-null pointers required",
-                          i, PD_EVAL_MAX_GT);
-    const int32_t rt = (d.p + kTP - 1) / kTP, ct = (d.g + kTG - 1) / kTG;
-    const int64_t chunks = (d.words + kWordsPerWg - 1) / kWordsPerWg;
-    h[i] = PairsEntry{d.a, d.rows, d.b, d.inter, d.words, d.p, d.g, rt, ct, (int32_t)chunks, 0, wgs};
-    wgs += (int64_t)rt * ct * chunks;
-  }
-  if (wgs >= INT32_MAX) return pd_set_error(PD_ERR_INVALID_ARG, "pd_eval_intersect_grouped: %lld workgroups", (long long)wgs);
   hipStream_t st = (hipStream_t)stream;
-  if (int rc = upload(h, count, table_device, st, "pd_eval_intersect_grouped")) return rc;
+  const int64_t wgs = stage_table<PairsEntry>(
+      "pd_eval_intersect_grouped", list, count, true, table_host_pinned, table_device, st,
+      [](const PdEvalPairs &d, int i, PairsEntry &e, int64_t wg_begin) -> int64_t {
+        if (d.p < 1 || d.g < 1 || d.g > PD_EVAL_MAX_GT || d.words < 1 || !d.a || !d.b || !d.inter)
+          return pd_set_error(PD_ERR_INVALID_ARG,
+                              "pd_eval_intersect_grouped: pair %d: p >= 1, 1 <= g <= %d, words >= 1, non-null pointers required", i,
+                              PD_EVAL_MAX_GT);
+        const int32_t rt = (d.p + kTP - 1) / kTP, ct = (d.g + kTG - 1) / kTG;
+        const int64_t chunks = (d.words + kWordsPerWg - 1) / kWordsPerWg;
+        e = PairsEntry{d.a, d.rows, d.b, d.inter, d.words, d.p, d.g, rt, ct, (int32_t)chunks, 0, wg_begin};
+        return (int64_t)rt * ct * chunks;
+      });
+  if (wgs <= 0) return (int)wgs;
   hipLaunchKernelGGL(eval_intersect, dim3((unsigned)wgs), dim3(kThreads), 0, st, (const PairsEntry *)table_device, count);
   return pd_check_launch("pd_eval_intersect_grouped");
 }
@@ -438,24 +414,21 @@ extern "C" int pd_eval_intersect_grouped(const PdEvalPairs *list, int32_t count,
 extern "C" int pd_eval_confusion_grouped(const PdEvalConfusion *list, int32_t count, int32_t n, int64_t *conf, int32_t num_slots,
                                          void *table_host_pinned, void *table_device, void *stream)
 {
-  if (count <= 0) return PD_OK;
-  if (!list || !conf || !table_host_pinned || !table_device) return pd_set_error(PD_ERR_INVALID_ARG, "pd_eval_confusion_grouped: null pointer");
-  if (n < 1 || n > 46340 || num_slots < 1)
-    return pd_set_error(PD_ERR_INVALID_ARG, "pd_eval_confusion_grouped: n = %d, num_slots = %d", n, num_slots);
-  ConfEntry *h = reinterpret_cast<ConfEntry *>(table_host_pinned);
-  int64_t wgs = 0;
-  for (int i = 0; i < count; ++i) {
-    const PdEvalConfusion &d = list[i];
-    if (d.pred_n < 0 || d.gt_n < 0 || d.hw <= 0 || !d.slot || (d.pred_n && (!d.pred_bits || !d.pred_cls)) || (d.gt_n && (!d.gt_bits || !d.gt_cls)))
-      return pd_set_error(PD_ERR_INVALID_ARG, "pd_eval_confusion_grouped: image %d: counts >= 0, hw > 0, non-null pointers required", i);
-    const int64_t words = (d.hw + 63) / 64;
-    const int64_t chunks = (words + kConfWordsPerWg - 1) / kConfWordsPerWg;
-    h[i] = ConfEntry{d.pred_bits, d.pred_cls, d.gt_bits, d.gt_cls, d.slot, d.hw, words, d.pred_n, d.gt_n, (int32_t)chunks, 0, wgs};
-    wgs += chunks;
-  }
-  if (wgs >= INT32_MAX) return pd_set_error(PD_ERR_INVALID_ARG, "pd_eval_confusion_grouped: %lld workgroups", (long long)wgs);
   hipStream_t st = (hipStream_t)stream;
-  if (int rc = upload(h, count, table_device, st, "pd_eval_confusion_grouped")) return rc;
+  const int64_t wgs = stage_table<ConfEntry>(
+      "pd_eval_confusion_grouped", list, count, conf != nullptr, table_host_pinned, table_device, st,
+      [=](const PdEvalConfusion &d, int i, ConfEntry &e, int64_t wg_begin) -> int64_t {
+        if (n < 1 || n > 46340 || num_slots < 1)                   // (the same for every i: answered at the first, before any descriptor)
+          return pd_set_error(PD_ERR_INVALID_ARG, "pd_eval_confusion_grouped: n = %d, num_slots = %d", n, num_slots);
+        if (d.pred_n < 0 || d.gt_n < 0 || d.hw <= 0 || !d.slot || (d.pred_n && (!d.pred_bits || !d.pred_cls)) ||
+            (d.gt_n && (!d.gt_bits || !d.gt_cls)))
+          return pd_set_error(PD_ERR_INVALID_ARG, "pd_eval_confusion_grouped: image %d: counts >= 0, hw > 0, non-null pointers required", i);
+        const int64_t words = (d.hw + 63) / 64;
+        const int64_t chunks = (words + kConfWordsPerWg - 1) / kConfWordsPerWg;
+        e = ConfEntry{d.pred_bits, d.pred_cls, d.gt_bits, d.gt_cls, d.slot, d.hw, words, d.pred_n, d.gt_n, (int32_t)chunks, 0, wg_begin};
+        return chunks;
+      });
+  if (wgs <= 0) return (int)wgs;
   const int64_t bins = (int64_t)(n + 1) * (n + 1);
   if (bins <= PD_EVAL_LDS_BINS)
     hipLaunchKernelGGL(eval_confusion<true>, dim3((unsigned)wgs), dim3(kThreads), (size_t)bins * sizeof(uint32_t), st,
@@ -469,20 +442,18 @@ extern "C" int pd_eval_confusion_grouped(const PdEvalConfusion *list, int32_t co
 extern "C" int pd_eval_recall_grouped(const PdEvalRecall *list, int32_t count, const float *thresholds, int64_t *hits, int64_t *num_pos,
                                       void *table_host_pinned, void *table_device, void *stream)
 {
-  if (count <= 0) return PD_OK;
-  if (!list || !thresholds || !hits || !num_pos || !table_host_pinned || !table_device)
-    return pd_set_error(PD_ERR_INVALID_ARG, "pd_eval_recall_grouped: null pointer");
-  RecallEntry *h = reinterpret_cast<RecallEntry *>(table_host_pinned);
-  for (int i = 0; i < count; ++i) {
-    const PdEvalRecall &d = list[i];
-    if (d.p < 1 || d.p > PD_EVAL_MAX_ROWS || d.g < 1 || d.g > PD_EVAL_MAX_GT || !d.inter || !d.area_p || !d.area_g)
-      return pd_set_error(PD_ERR_INVALID_ARG, "pd_eval_recall_grouped: image %d: 1 <= p <= %d, 1 <= g <= %d, non-null pointers required", i,
-                          PD_EVAL_MAX_ROWS, PD_EVAL_MAX_GT);
-    h[i] = RecallEntry{d.inter, d.rows, d.area_p, d.area_g, d.p, d.g, i};
-  }
   hipStream_t st = (hipStream_t)stream;
-  if (int rc = upload(h, count, table_device, st, "pd_eval_recall_grouped")) return rc;
-  hipLaunchKernelGGL(eval_recall, dim3((unsigned)count), dim3(kRecallThreads), 0, st, (const RecallEntry *)table_device, thresholds, hits,
+  const int64_t wgs = stage_table<RecallEntry>(                    // one workgroup per image: wg_begin = i
+      "pd_eval_recall_grouped", list, count, thresholds && hits && num_pos, table_host_pinned, table_device, st,
+      [](const PdEvalRecall &d, int i, RecallEntry &e, int64_t wg_begin) -> int64_t {
+        if (d.p < 1 || d.p > PD_EVAL_MAX_ROWS || d.g < 1 || d.g > PD_EVAL_MAX_GT || !d.inter || !d.area_p || !d.area_g)
+          return pd_set_error(PD_ERR_INVALID_ARG, "pd_eval_recall_grouped: image %d: 1 <= p <= %d, 1 <= g <= %d, non-null pointers required", i,
+                              PD_EVAL_MAX_ROWS, PD_EVAL_MAX_GT);
+        e = RecallEntry{d.inter, d.rows, d.area_p, d.area_g, d.p, d.g, wg_begin};
+        return 1;
+      });
+  if (wgs <= 0) return (int)wgs;
+  hipLaunchKernelGGL(eval_recall, dim3((unsigned)wgs), dim3(kRecallThreads), 0, st, (const RecallEntry *)table_device, thresholds, hits,
                      num_pos);
   return pd_check_launch("pd_eval_recall_grouped");
 }

@@ -6,19 +6,9 @@
 #include "pd_common.h"
 #include "pd_grouping.h"
 #include "pd_msda.h"
+#include "resize_taps.h"
 
 namespace {
-
-// torch upsample_bilinear2d (align_corners = false) source index
-__device__ __forceinline__ void src_index(int dst, float scale, int in_size, int &i0, int &ip, float &l0, float &l1)
-{
-  float src = scale * (dst + 0.5f) - 0.5f;
-  src = src < 0.f ? 0.f : src;
-  i0 = (int)src;
-  ip = (i0 < in_size - 1) ? 1 : 0;
-  l1 = src - i0;
-  l0 = 1.f - l1;
-}
 
 __global__ __launch_bounds__(256) void scores_argmax_u8(const float *__restrict__ scores, const uint8_t *__restrict__ mask,
                                                         uint8_t *__restrict__ labels, int K, int h, int w, float sh, float sw,
@@ -36,7 +26,7 @@ __global__ __launch_bounds__(256) void scores_argmax_u8(const float *__restrict_
   int arg = 0;
   for (int k = 0; k < K; ++k) {
     const float *s = scores + (int64_t)k * h * w;
-    const float v = hy0 * (wx0 * s[a] + wx1 * s[b]) + hy1 * (wx0 * s[c] + wx1 * s[d]);
+    const float v = bilinear2x2(s, a, b, c, d, hy0, hy1, wx0, wx1);
     if (v > best) { best = v; arg = k; }
   }
   labels[o] = (uint8_t)(arg + 1);
@@ -69,7 +59,7 @@ __global__ __launch_bounds__(256) void mask_assign(const float *__restrict__ log
     float v = 0.f;
     if (inside) {
       const float *s = logits + (int64_t)k * h * w;
-      v = (hy0 * (wx0 * s[a] + wx1 * s[b]) + hy1 * (wx0 * s[c] + wx1 * s[d])) * om;
+      v = bilinear2x2(s, a, b, c, d, hy0, hy1, wx0, wx1) * om;
     }
     const bool pos = inside && v > 0.f;
     const unsigned long long bal = __ballot(pos);

@@ -6,7 +6,8 @@
 
 #include "pd_common.h"
 #include "pd_assign.h"
-#include "pd_msda.h"                         // PD_OK / PD_ERR_*
+#include "grouped_table.h"
+#include "resize_taps.h"
 
 namespace {
 
@@ -19,67 +20,12 @@ constexpr int kHistPx = 8;                   // consecutive pixels per thread an
 constexpr int kHistSteps = 4;                // steps per workgroup: 8192 pixels
 constexpr int kHistBins = 8192;              // int32 bins of a workgroup's LDS histogram
 
-template <typename E>
-__device__ __forceinline__ const E *find_entry(const E *table, int count, int64_t wg)
-{
-  int e = 0;
-  while (e + 1 < count && wg >= table[e + 1].wg_begin) ++e;
-  return pd_as_global(table + e);
-}
-
-// ATen's area_pixel_compute_source_index (align_corners = false) and the two taps of upsample_bilinear2d, every operation rounded on its
-// own: contraction is switched off inside tap_of (see csrc/pixel_grouping.hip)
-struct Tap {
-  int i0, i1;
-  float l0, l1;
-};
-
-__device__ __forceinline__ Tap tap_of(int dst, float scale, int in_size)
-{
-#pragma clang fp contract(off)
-  float src = scale * ((float)dst + 0.5f) - 0.5f;
-  src = src < 0.f ? 0.f : src;
-  Tap t;
-  t.i0 = (int)src;
-  t.i0 = t.i0 < in_size - 1 ? t.i0 : in_size - 1;
-  t.i1 = t.i0 + (t.i0 < in_size - 1 ? 1 : 0);
-  t.l1 = src - (float)t.i0;
-  t.l0 = 1.f - t.l1;
-  return t;
-}
-
-// the two chained interpolations along one axis: output index -> 4 low-resolution indices (i[0] the smallest, i[3] the largest) and weights
-struct Tap4 {
-  int i[4];
-  float w[4];
-};
-
-__device__ __forceinline__ Tap4 chain_of(int dst, float scale2, int crop, float scale1, int low)
-{
-  const Tap o = tap_of(dst, scale2, crop);
-  const Tap a = tap_of(o.i0, scale1, low), b = tap_of(o.i1, scale1, low);
-  Tap4 t;
-  t.i[0] = a.i0, t.i[1] = a.i1, t.i[2] = b.i0, t.i[3] = b.i1;
-  t.w[0] = o.l0 * a.l0, t.w[1] = o.l0 * a.l1, t.w[2] = o.l1 * b.l0, t.w[3] = o.l1 * b.l1;
-  return t;
-}
-
-// the source index of pd_mask_assign (csrc/grouping.hip), kept word for word: the identity case promises its bits
-__device__ __forceinline__ void src_index(int dst, float scale, int in_size, int &i0, int &ip, float &l0, float &l1)
-{
-  float src = scale * (dst + 0.5f) - 0.5f;
-  src = src < 0.f ? 0.f : src;
-  i0 = (int)src;
-  ip = (i0 < in_size - 1) ? 1 : 0;
-  l1 = src - i0;
-  l0 = 1.f - l1;
-}
-
 // ------------------------------------------------------------------------------------------------------------------- assignment
 // One wavefront per output row segment of 256 pixels.  K runs up to 256, so the row mix of pd_scores_argmax_resized_u8 (the 4
 // low-resolution rows of the output row combined once per (k, low column) into LDS) is walked in chunks of k that fit kMixFloats; the
 // per-pixel state (best product, its k, the largest v) lives in registers across the chunks.  A segment whose column span leaves fewer
-// than kMinChunk k per chunk (strong down-scaling) mixes per pixel from memory; the identity case evaluates pd_mask_assign's expression.
+// than kMinChunk k per chunk (strong down-scaling) mixes per pixel from memory; the identity case evaluates pd_mask_assign's expression
+// (src_index and bilinear2x2 of resize_taps.h, which csrc/grouping.hip uses too).
 // Segments without an object pixel have v_k = 0 for every k: they write the first arg-max of the scores and obj = 0.
 struct AssignEntry {
   const float *logits;
@@ -177,7 +123,7 @@ __global__ void __launch_bounds__(kThreads) mask_assign_resized(const AssignEntr
           v[j] = 0.f;
           if (in[j]) {
             const int a = y0 * w + c0[j], b = a + cp[j], c = (y0 + yp) * w + c0[j], d = c + cp[j];
-            v[j] = (hy0 * (wx0[j] * s[a] + wx1[j] * s[b]) + hy1 * (wx0[j] * s[c] + wx1[j] * s[d])) * om[j];
+            v[j] = bilinear2x2(s, a, b, c, d, hy0, hy1, wx0[j], wx1[j]) * om[j];
           }
         }
         consume(k, v);
@@ -192,7 +138,7 @@ __global__ void __launch_bounds__(kThreads) mask_assign_resized(const AssignEntr
     }
     auto rowmix = [&](int k, int c) {
       const float *s = logits + k * hw + c;
-      return (ry.w[0] * s[ry.i[0] * w] + ry.w[1] * s[ry.i[1] * w]) + (ry.w[2] * s[ry.i[2] * w] + ry.w[3] * s[ry.i[3] * w]);
+      return mix4(ry, [&](int i) { return s[i * w]; });
     };
     if (use_lds) {
       float *mix = mix_s[wave];
@@ -210,8 +156,7 @@ __global__ void __launch_bounds__(kThreads) mask_assign_resized(const AssignEntr
             float v[kPx];
 #pragma unroll
             for (int j = 0; j < kPx; ++j)
-              v[j] = ((cx[j].w[0] * mix[b + cx[j].i[0]] + cx[j].w[1] * mix[b + cx[j].i[1]]) +
-                      (cx[j].w[2] * mix[b + cx[j].i[2]] + cx[j].w[3] * mix[b + cx[j].i[3]])) * om[j];
+              v[j] = mix4(cx[j], [=](int i) { return mix[b + i]; }) * om[j];
             consume(k0 + k, v);
           }
         __syncthreads();
@@ -223,8 +168,7 @@ __global__ void __launch_bounds__(kThreads) mask_assign_resized(const AssignEntr
         for (int j = 0; j < kPx; ++j) {
           v[j] = 0.f;
           if (in[j])
-            v[j] = ((cx[j].w[0] * rowmix(k, cx[j].i[0]) + cx[j].w[1] * rowmix(k, cx[j].i[1])) +
-                    (cx[j].w[2] * rowmix(k, cx[j].i[2]) + cx[j].w[3] * rowmix(k, cx[j].i[3]))) * om[j];
+            v[j] = mix4(cx[j], [&](int i) { return rowmix(k, i); }) * om[j];
         }
         consume(k, v);
       }
@@ -257,26 +201,11 @@ __global__ void __launch_bounds__(kThreads) mask_assign_resized(const AssignEntr
     int16_t *ap = arg + o;
     uint8_t *op = obj + o;
     const bool full = in[kPx - 1];
-    if (full && ((uintptr_t)ap & 7) == 0) {
-      uint2 v;
-      v.x = (uint32_t)(uint16_t)besti[0] | ((uint32_t)(uint16_t)besti[1] << 16);
-      v.y = (uint32_t)(uint16_t)besti[2] | ((uint32_t)(uint16_t)besti[3] << 16);
-      *reinterpret_cast<uint2 *>(ap) = v;
-    } else {
-#pragma unroll
-      for (int j = 0; j < kPx; ++j)
-        if (in[j]) ap[j] = (int16_t)besti[j];
-    }
-    if (full && ((uintptr_t)op & 3) == 0) {
-      *reinterpret_cast<uint32_t *>(op) = (uint32_t)ob[0] | ((uint32_t)ob[1] << 8) | ((uint32_t)ob[2] << 16) | ((uint32_t)ob[3] << 24);
-    } else {
-#pragma unroll
-      for (int j = 0; j < kPx; ++j)
-        if (in[j]) op[j] = ob[j];
-    }
+    store4_i16(ap, full && aligned8(ap), in, besti);
+    store4_u8(op, full && aligned4(op), in, pack4_u8(ob));
     if (cls) {
       int16_t *cp = cls + o;
-      if (full && ((uintptr_t)cp & 7) == 0) {
+      if (full && aligned8(cp)) {                                              // (written out: store4_i16 here changes the kernel's instruction stream)
         uint2 v;
         v.x = (uint32_t)(uint16_t)cl[0] | ((uint32_t)(uint16_t)cl[1] << 16);
         v.y = (uint32_t)(uint16_t)cl[2] | ((uint32_t)(uint16_t)cl[3] << 16);
@@ -430,13 +359,6 @@ __global__ void __launch_bounds__(kThreads) assign_histogram(const HistEntry *ta
   }
 }
 
-int upload(const void *h, size_t bytes, void *table_device, hipStream_t st, const char *what)
-{
-  if (hipMemcpyAsync(table_device, h, bytes, hipMemcpyHostToDevice, st) != hipSuccess)
-    return pd_set_error(PD_ERR_LAUNCH, "%s: table upload failed", what);
-  return PD_OK;
-}
-
 }  // namespace
 
 extern "C" int64_t pd_assign_table_bytes(int32_t count)
@@ -447,52 +369,44 @@ extern "C" int64_t pd_assign_table_bytes(int32_t count)
 
 extern "C" int pd_mask_assign_resized(const PdAssignResized *list, int32_t count, void *table_host_pinned, void *table_device, void *stream)
 {
-  if (count <= 0) return PD_OK;
-  if (!list || !table_host_pinned || !table_device) return pd_set_error(PD_ERR_INVALID_ARG, "pd_mask_assign_resized: null pointer");
-  AssignEntry *hst = reinterpret_cast<AssignEntry *>(table_host_pinned);
-  int64_t wgs = 0;
-  for (int i = 0; i < count; ++i) {
-    const PdAssignResized &d = list[i];
-    if (d.K < 1 || d.K > PD_ASSIGN_MAX_K || d.h <= 0 || d.w <= 0 || d.Hp <= 0 || d.Wp <= 0 || d.Hi <= 0 || d.Wi <= 0 || d.Hi > d.Hp ||
-        d.Wi > d.Wp || d.H <= 0 || d.W <= 0 || (int64_t)d.K * d.h * d.w >= INT32_MAX || !d.logits || !d.scores || !d.arg || !d.obj ||
-        !d.positive)
-      return pd_set_error(PD_ERR_INVALID_ARG,
-                          "pd_mask_assign_resized: image %d: K=%d h=%d w=%d Hp=%d Wp=%d Hi=%d Wi=%d H=%d W=%d (1 <= K <= %d, Hi <= Hp, "
-                          "Wi <= Wp, non-null logits / scores / arg / obj / positive required)",
-                          i, d.K, d.h, d.w, d.Hp, d.Wp, d.Hi, d.Wi, d.H, d.W, PD_ASSIGN_MAX_K);
-    const int32_t tiles_x = (d.W + kTileW - 1) / kTileW, tiles_y = (d.H + kWaves - 1) / kWaves;
-    hst[i] = AssignEntry{d.logits, d.scores, d.object, d.cls_of_query, d.arg, d.obj, d.positive, d.cls, d.K, d.h, d.w, d.Hi, d.Wi, d.H, d.W,
-                         tiles_x, (d.H == d.Hi && d.W == d.Wi) ? 1 : 0, 0,
-                         (float)d.h / (float)d.Hp, (float)d.w / (float)d.Wp, (float)d.Hi / (float)d.H, (float)d.Wi / (float)d.W, wgs};
-    wgs += (int64_t)tiles_x * tiles_y;
-  }
-  if (wgs >= INT32_MAX) return pd_set_error(PD_ERR_INVALID_ARG, "pd_mask_assign_resized: %lld workgroups", (long long)wgs);
   hipStream_t st = (hipStream_t)stream;
-  if (int rc = upload(hst, (size_t)count * sizeof(AssignEntry), table_device, st, "pd_mask_assign_resized")) return rc;
+  const int64_t wgs = stage_table<AssignEntry>(
+      "pd_mask_assign_resized", list, count, true, table_host_pinned, table_device, st,
+      [](const PdAssignResized &d, int i, AssignEntry &e, int64_t wg_begin) -> int64_t {
+        if (d.K < 1 || d.K > PD_ASSIGN_MAX_K || d.h <= 0 || d.w <= 0 || d.Hp <= 0 || d.Wp <= 0 || d.Hi <= 0 || d.Wi <= 0 || d.Hi > d.Hp ||
+            d.Wi > d.Wp || d.H <= 0 || d.W <= 0 || (int64_t)d.K * d.h * d.w >= INT32_MAX || !d.logits || !d.scores || !d.arg || !d.obj ||
+            !d.positive)
+          return pd_set_error(PD_ERR_INVALID_ARG,
+                              "pd_mask_assign_resized: image %d: K=%d h=%d w=%d Hp=%d Wp=%d Hi=%d Wi=%d H=%d W=%d (1 <= K <= %d, Hi <= Hp, "
+                              "Wi <= Wp, non-null logits / scores / arg / obj / positive required)",
+                              i, d.K, d.h, d.w, d.Hp, d.Wp, d.Hi, d.Wi, d.H, d.W, PD_ASSIGN_MAX_K);
+        const int32_t tiles_x = (d.W + kTileW - 1) / kTileW, tiles_y = (d.H + kWaves - 1) / kWaves;
+        e = AssignEntry{d.logits, d.scores, d.object, d.cls_of_query, d.arg, d.obj, d.positive, d.cls, d.K, d.h, d.w, d.Hi, d.Wi, d.H, d.W,
+                        tiles_x, (d.H == d.Hi && d.W == d.Wi) ? 1 : 0, 0,
+                        (float)d.h / (float)d.Hp, (float)d.w / (float)d.Wp, (float)d.Hi / (float)d.H, (float)d.Wi / (float)d.W, wg_begin};
+        return (int64_t)tiles_x * tiles_y;
+      });
+  if (wgs <= 0) return (int)wgs;
   hipLaunchKernelGGL(mask_assign_resized, dim3((unsigned)wgs), dim3(kThreads), 0, st, (const AssignEntry *)table_device, count);
   return pd_check_launch("pd_mask_assign_resized");
 }
 
 extern "C" int pd_assign_histogram(const PdAssignHistogram *list, int32_t count, void *table_host_pinned, void *table_device, void *stream)
 {
-  if (count <= 0) return PD_OK;
-  if (!list || !table_host_pinned || !table_device) return pd_set_error(PD_ERR_INVALID_ARG, "pd_assign_histogram: null pointer");
-  HistEntry *hst = reinterpret_cast<HistEntry *>(table_host_pinned);
-  int64_t wgs = 0;
-  const int64_t per_wg = (int64_t)kThreads * kHistPx * kHistSteps;
-  for (int i = 0; i < count; ++i) {
-    const PdAssignHistogram &d = list[i];
-    if (d.n < 1 || d.n > PD_ASSIGN_MAX_KEYS || d.G < 0 || d.G > PD_ASSIGN_MAX_GT || d.hw <= 0 || !d.key || !d.obj || !d.won || !d.area ||
-        (d.G > 0 && (!d.gt || !d.inter || !d.gt_area)))
-      return pd_set_error(PD_ERR_INVALID_ARG,
-                          "pd_assign_histogram: image %d: n=%d G=%d hw=%lld (1 <= n <= %d, 0 <= G <= %d, hw > 0, non-null pointers required)", i,
-                          d.n, d.G, (long long)d.hw, PD_ASSIGN_MAX_KEYS, PD_ASSIGN_MAX_GT);
-    hst[i] = HistEntry{d.key, d.obj, d.gt, d.won, d.area, d.inter, d.gt_area, d.n, d.G, d.hw, wgs};
-    wgs += (d.hw + per_wg - 1) / per_wg;
-  }
-  if (wgs >= INT32_MAX) return pd_set_error(PD_ERR_INVALID_ARG, "pd_assign_histogram: %lld workgroups", (long long)wgs);
   hipStream_t st = (hipStream_t)stream;
-  if (int rc = upload(hst, (size_t)count * sizeof(HistEntry), table_device, st, "pd_assign_histogram")) return rc;
+  const int64_t wgs = stage_table<HistEntry>(
+      "pd_assign_histogram", list, count, true, table_host_pinned, table_device, st,
+      [](const PdAssignHistogram &d, int i, HistEntry &e, int64_t wg_begin) -> int64_t {
+        if (d.n < 1 || d.n > PD_ASSIGN_MAX_KEYS || d.G < 0 || d.G > PD_ASSIGN_MAX_GT || d.hw <= 0 || !d.key || !d.obj || !d.won || !d.area ||
+            (d.G > 0 && (!d.gt || !d.inter || !d.gt_area)))
+          return pd_set_error(PD_ERR_INVALID_ARG,
+                              "pd_assign_histogram: image %d: n=%d G=%d hw=%lld (1 <= n <= %d, 0 <= G <= %d, hw > 0, non-null pointers required)",
+                              i, d.n, d.G, (long long)d.hw, PD_ASSIGN_MAX_KEYS, PD_ASSIGN_MAX_GT);
+        const int64_t per_wg = (int64_t)kThreads * kHistPx * kHistSteps;
+        e = HistEntry{d.key, d.obj, d.gt, d.won, d.area, d.inter, d.gt_area, d.n, d.G, d.hw, wg_begin};
+        return (d.hw + per_wg - 1) / per_wg;
+      });
+  if (wgs <= 0) return (int)wgs;
   hipLaunchKernelGGL(assign_histogram, dim3((unsigned)wgs), dim3(kThreads), 0, st, (const HistEntry *)table_device, count);
   return pd_check_launch("pd_assign_histogram");
 }

@@ -8,7 +8,8 @@
 
 #include "pd_common.h"
 #include "pd_grouping.h"
-#include "pd_msda.h"                         // PD_OK / PD_ERR_*
+#include "grouped_table.h"
+#include "resize_taps.h"
 
 namespace {
 
@@ -17,55 +18,6 @@ constexpr int kPx = 4;                       // pixels per lane
 constexpr int kTileW = 64 * kPx;             // columns per workgroup
 constexpr int kMixFloats = 1024;             // row-mixed scores a wavefront keeps in LDS: K * (low-resolution columns under its 256 pixels)
 constexpr int kResizeRows = 4;               // rows per wavefront of masks_resize
-
-template <typename E>
-__device__ __forceinline__ const E *find_entry(const E *table, int count, int64_t wg)
-{
-  int e = 0;
-  while (e + 1 < count && wg >= table[e + 1].wg_begin) ++e;
-  return pd_as_global(table + e);
-}
-
-// ATen's area_pixel_compute_source_index (align_corners = false) and the two taps of upsample_bilinear2d, every operation rounded on its
-// own: contraction is switched off inside tap_of (HIP's default would fuse scale * (dst + 0.5) - 0.5 into one fma, and whether l1 is
-// exactly 0 decides a mask pixel)
-struct Tap {
-  int i0, i1;
-  float l0, l1;
-};
-
-__device__ __forceinline__ Tap tap_of(int dst, float scale, int in_size)
-{
-#pragma clang fp contract(off)
-  float src = scale * ((float)dst + 0.5f) - 0.5f;
-  src = src < 0.f ? 0.f : src;
-  Tap t;
-  t.i0 = (int)src;
-  t.i0 = t.i0 < in_size - 1 ? t.i0 : in_size - 1;
-  t.i1 = t.i0 + (t.i0 < in_size - 1 ? 1 : 0);
-  t.l1 = src - (float)t.i0;
-  t.l0 = 1.f - t.l1;
-  return t;
-}
-
-// the two chained interpolations along one axis: output index -> 4 low-resolution indices (i[0] the smallest, i[3] the largest; the
-// middle two in no fixed order) and their weights
-struct Tap4 {
-  int i[4];
-  float w[4];
-};
-
-__device__ __forceinline__ Tap4 chain_of(int dst, float scale2, int crop, float scale1, int low)
-{
-  const Tap o = tap_of(dst, scale2, crop);
-  const Tap a = tap_of(o.i0, scale1, low), b = tap_of(o.i1, scale1, low);
-  Tap4 t;
-  t.i[0] = a.i0, t.i[1] = a.i1, t.i[2] = b.i0, t.i[3] = b.i1;
-  t.w[0] = o.l0 * a.l0, t.w[1] = o.l0 * a.l1, t.w[2] = o.l1 * b.l0, t.w[3] = o.l1 * b.l1;
-  return t;
-}
-
-__device__ __forceinline__ bool aligned4(const void *p) { return ((uintptr_t)p & 3) == 0; }
 
 // ------------------------------------------------------------------------------------------------------------------- label map
 // One wavefront per output row segment of 256 pixels.  The row's 4 low-resolution rows are mixed once per (k, low column) into LDS
@@ -105,18 +57,7 @@ __global__ void __launch_bounds__(kThreads) scores_argmax_resized(const LabelsEn
   bool in[kPx];
 #pragma unroll
   for (int j = 0; j < kPx; ++j) in[j] = row_ok && x0 + j < W;
-  if (in[0]) {
-    const uint8_t *mp = mask + o;
-    if (in[kPx - 1] && aligned4(mp)) {
-      const uint32_t v = *reinterpret_cast<const uint32_t *>(mp);
-#pragma unroll
-      for (int j = 0; j < kPx; ++j) m[j] = (uint8_t)(v >> (8 * j));
-    } else {
-#pragma unroll
-      for (int j = 0; j < kPx; ++j)
-        if (in[j]) m[j] = mp[j];
-    }
-  }
+  if (in[0]) load4_u8(mask + o, in[kPx - 1] && aligned4(mask + o), in, m);
   const bool any = __ballot((m[0] | m[1] | m[2] | m[3]) != 0) != 0;          // wave-uniform: this segment has object pixels
 
   Tap4 ry;
@@ -125,12 +66,12 @@ __global__ void __launch_bounds__(kThreads) scores_argmax_resized(const LabelsEn
   float *mix = mix_s[wave];
   auto rowmix = [&](int k, int c) {
     const float *s = scores + (int64_t)k * h * w + c;
-    return (ry.w[0] * s[ry.i[0] * w] + ry.w[1] * s[ry.i[1] * w]) + (ry.w[2] * s[ry.i[2] * w] + ry.w[3] * s[ry.i[3] * w]);
+    return mix4(ry, [&](int i) { return s[i * w]; });
   };
   if (any) {
     ry = chain_of(y, e->sh2, e->Hi, e->sh1, h);
     const int xe = (xs + kTileW < W ? xs + kTileW : W) - 1;
-    // the taps are non-decreasing in the output index (every step of tap_of is monotone): first tap of the first pixel, last of the last
+    // the taps are non-decreasing in the output index (resize_taps.h): first tap of the first pixel, last of the last
     cmin = chain_of(xs, e->sw2, e->Wi, e->sw1, w).i[0];
     ncols = chain_of(xe, e->sw2, e->Wi, e->sw1, w).i[3] - cmin + 1;
     use_lds = ncols * K <= kMixFloats;
@@ -156,9 +97,9 @@ __global__ void __launch_bounds__(kThreads) scores_argmax_resized(const LabelsEn
         float v;
         if (use_lds) {
           const int b = k * ncols - cmin;
-          v = (cx.w[0] * mix[b + cx.i[0]] + cx.w[1] * mix[b + cx.i[1]]) + (cx.w[2] * mix[b + cx.i[2]] + cx.w[3] * mix[b + cx.i[3]]);
+          v = mix4(cx, [&](int i) { return mix[b + i]; });
         } else {
-          v = (cx.w[0] * rowmix(k, cx.i[0]) + cx.w[1] * rowmix(k, cx.i[1])) + (cx.w[2] * rowmix(k, cx.i[2]) + cx.w[3] * rowmix(k, cx.i[3]));
+          v = mix4(cx, [&rowmix, k](int i) { return rowmix(k, i); });
         }
         if (v > best) {
           best = v;
@@ -168,16 +109,7 @@ __global__ void __launch_bounds__(kThreads) scores_argmax_resized(const LabelsEn
       lab[j] = (uint8_t)(arg + 1);
     }
   }
-  if (in[0]) {
-    uint8_t *lp = labels + o;
-    if (in[kPx - 1] && aligned4(lp)) {
-      *reinterpret_cast<uint32_t *>(lp) = (uint32_t)lab[0] | ((uint32_t)lab[1] << 8) | ((uint32_t)lab[2] << 16) | ((uint32_t)lab[3] << 24);
-    } else {
-#pragma unroll
-      for (int j = 0; j < kPx; ++j)
-        if (in[j]) lp[j] = lab[j];
-    }
-  }
+  if (in[0]) store4_u8(labels + o, in[kPx - 1] && aligned4(labels + o), in, pack4_u8(lab));
   // label counts: per wavefront by ballot, per workgroup in LDS, one global atomic per label present
   for (int l = 0; l <= K; ++l) {
     int c = 0;
@@ -264,13 +196,6 @@ __global__ void __launch_bounds__(kThreads) masks_resize(const ResizeEntry *tabl
   }
 }
 
-int upload(const void *h, size_t bytes, void *table_device, hipStream_t st, const char *what)
-{
-  if (hipMemcpyAsync(table_device, h, bytes, hipMemcpyHostToDevice, st) != hipSuccess)
-    return pd_set_error(PD_ERR_LAUNCH, "%s: table upload failed", what);
-  return PD_OK;
-}
-
 bool sizes_ok(int Hp, int Wp, int Hi, int Wi, int H, int W)
 {
   return Hp > 0 && Wp > 0 && Hi > 0 && Wi > 0 && Hi <= Hp && Wi <= Wp && H > 0 && W > 0;
@@ -286,52 +211,43 @@ extern "C" int64_t pd_grouping_table_bytes(int32_t count)
 
 extern "C" int pd_scores_argmax_resized_u8(const PdGroupLabels *list, int32_t count, void *table_host_pinned, void *table_device, void *stream)
 {
-  if (count <= 0) return PD_OK;
-  if (!list || !table_host_pinned || !table_device) return pd_set_error(PD_ERR_INVALID_ARG, "pd_scores_argmax_resized_u8: null pointer");
-  LabelsEntry *hst = reinterpret_cast<LabelsEntry *>(table_host_pinned);
-  int64_t wgs = 0;
-  for (int i = 0; i < count; ++i) {
-    const PdGroupLabels &d = list[i];
-    if (d.K < 1 || d.K > PD_GROUPING_MAX_K || d.h <= 0 || d.w <= 0 || !sizes_ok(d.Hp, d.Wp, d.Hi, d.Wi, d.H, d.W) ||
-        (int64_t)d.K * d.h * d.w >= INT32_MAX || !d.scores || !d.mask || !d.labels || !d.counts)
-      return pd_set_error(PD_ERR_INVALID_ARG,
-                          "pd_scores_argmax_resized_u8: image %d: K=%d h=%d w=%d Hp=%d Wp=%d Hi=%d Wi=%d H=%d W=%d (1 <= K <= %d, Hi <= Hp, "
-                          "Wi <= Wp, non-null pointers required)",
-                          i, d.K, d.h, d.w, d.Hp, d.Wp, d.Hi, d.Wi, d.H, d.W, PD_GROUPING_MAX_K);
-    const int32_t tiles_x = (d.W + kTileW - 1) / kTileW, tiles_y = (d.H + kWaves - 1) / kWaves;
-    hst[i] = LabelsEntry{d.scores, d.mask, d.labels, d.counts, d.K, d.h, d.w, d.Hi, d.Wi, d.H, d.W, tiles_x,
-                         (float)d.h / (float)d.Hp, (float)d.w / (float)d.Wp, (float)d.Hi / (float)d.H, (float)d.Wi / (float)d.W, wgs};
-    wgs += (int64_t)tiles_x * tiles_y;
-  }
-  if (wgs >= INT32_MAX) return pd_set_error(PD_ERR_INVALID_ARG, "pd_scores_argmax_resized_u8: %lld workgroups", (long long)wgs);
   hipStream_t st = (hipStream_t)stream;
-  if (int rc = upload(hst, (size_t)count * sizeof(LabelsEntry), table_device, st, "pd_scores_argmax_resized_u8")) return rc;
+  const int64_t wgs = stage_table<LabelsEntry>(
+      "pd_scores_argmax_resized_u8", list, count, true, table_host_pinned, table_device, st,
+      [](const PdGroupLabels &d, int i, LabelsEntry &e, int64_t wg_begin) -> int64_t {
+        if (d.K < 1 || d.K > PD_GROUPING_MAX_K || d.h <= 0 || d.w <= 0 || !sizes_ok(d.Hp, d.Wp, d.Hi, d.Wi, d.H, d.W) ||
+            (int64_t)d.K * d.h * d.w >= INT32_MAX || !d.scores || !d.mask || !d.labels || !d.counts)
+          return pd_set_error(PD_ERR_INVALID_ARG,
+                              "pd_scores_argmax_resized_u8: image %d: K=%d h=%d w=%d Hp=%d Wp=%d Hi=%d Wi=%d H=%d W=%d (1 <= K <= %d, Hi <= Hp, "
+                              "Wi <= Wp, non-null pointers required)",
+                              i, d.K, d.h, d.w, d.Hp, d.Wp, d.Hi, d.Wi, d.H, d.W, PD_GROUPING_MAX_K);
+        const int32_t tiles_x = (d.W + kTileW - 1) / kTileW, tiles_y = (d.H + kWaves - 1) / kWaves;
+        e = LabelsEntry{d.scores, d.mask, d.labels, d.counts, d.K, d.h, d.w, d.Hi, d.Wi, d.H, d.W, tiles_x,
+                        (float)d.h / (float)d.Hp, (float)d.w / (float)d.Wp, (float)d.Hi / (float)d.H, (float)d.Wi / (float)d.W, wg_begin};
+        return (int64_t)tiles_x * tiles_y;
+      });
+  if (wgs <= 0) return (int)wgs;
   hipLaunchKernelGGL(scores_argmax_resized, dim3((unsigned)wgs), dim3(kThreads), 0, st, (const LabelsEntry *)table_device, count);
   return pd_check_launch("pd_scores_argmax_resized_u8");
 }
 
 extern "C" int pd_masks_resize_u8(const PdMaskResize *list, int32_t count, void *table_host_pinned, void *table_device, void *stream)
 {
-  if (count <= 0) return PD_OK;
-  if (!list || !table_host_pinned || !table_device) return pd_set_error(PD_ERR_INVALID_ARG, "pd_masks_resize_u8: null pointer");
-  ResizeEntry *hst = reinterpret_cast<ResizeEntry *>(table_host_pinned);
-  int64_t wgs = 0;
-  for (int i = 0; i < count; ++i) {
-    const PdMaskResize &d = list[i];
-    if (d.n < 0 || !sizes_ok(d.Hp, d.Wp, d.Hi, d.Wi, d.H, d.W) || (d.n > 0 && (!d.src || !d.dst || !d.area)))
-      return pd_set_error(PD_ERR_INVALID_ARG,
-                          "pd_masks_resize_u8: image %d: n=%d Hp=%d Wp=%d Hi=%d Wi=%d H=%d W=%d (n >= 0, Hi <= Hp, Wi <= Wp, non-null pointers "
-                          "required)",
-                          i, d.n, d.Hp, d.Wp, d.Hi, d.Wi, d.H, d.W);
-    const int32_t tiles_x = (d.W + kTileW - 1) / kTileW, tiles_y = (d.H + kWaves * kResizeRows - 1) / (kWaves * kResizeRows);
-    hst[i] = ResizeEntry{d.src, d.dst, d.area, d.n, d.Hp, d.Wp, d.Hi, d.Wi, d.H, d.W, tiles_x, tiles_y, 0,
-                         (float)d.Hi / (float)d.H, (float)d.Wi / (float)d.W, wgs};
-    wgs += (int64_t)tiles_x * tiles_y * d.n;
-  }
-  if (wgs == 0) return PD_OK;
-  if (wgs >= INT32_MAX) return pd_set_error(PD_ERR_INVALID_ARG, "pd_masks_resize_u8: %lld workgroups", (long long)wgs);
   hipStream_t st = (hipStream_t)stream;
-  if (int rc = upload(hst, (size_t)count * sizeof(ResizeEntry), table_device, st, "pd_masks_resize_u8")) return rc;
+  const int64_t wgs = stage_table<ResizeEntry>(
+      "pd_masks_resize_u8", list, count, true, table_host_pinned, table_device, st,
+      [](const PdMaskResize &d, int i, ResizeEntry &e, int64_t wg_begin) -> int64_t {
+        if (d.n < 0 || !sizes_ok(d.Hp, d.Wp, d.Hi, d.Wi, d.H, d.W) || (d.n > 0 && (!d.src || !d.dst || !d.area)))
+          return pd_set_error(PD_ERR_INVALID_ARG,
+                              "pd_masks_resize_u8: image %d: n=%d Hp=%d Wp=%d Hi=%d Wi=%d H=%d W=%d (n >= 0, Hi <= Hp, Wi <= Wp, non-null "
+                              "pointers required)",
+                              i, d.n, d.Hp, d.Wp, d.Hi, d.Wi, d.H, d.W);
+        const int32_t tiles_x = (d.W + kTileW - 1) / kTileW, tiles_y = (d.H + kWaves * kResizeRows - 1) / (kWaves * kResizeRows);
+        e = ResizeEntry{d.src, d.dst, d.area, d.n, d.Hp, d.Wp, d.Hi, d.Wi, d.H, d.W, tiles_x, tiles_y, 0,
+                        (float)d.Hi / (float)d.H, (float)d.Wi / (float)d.W, wg_begin};
+        return (int64_t)tiles_x * tiles_y * d.n;
+      });
+  if (wgs <= 0) return (int)wgs;
   hipLaunchKernelGGL(masks_resize, dim3((unsigned)wgs), dim3(kThreads), 0, st, (const ResizeEntry *)table_device, count);
   return pd_check_launch("pd_masks_resize_u8");
 }

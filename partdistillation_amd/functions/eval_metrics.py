@@ -4,13 +4,16 @@ batch of images (a descriptor table staged through a pinned ring), and none read
 
 Bit planes are int64 tensors [n, ceil(H*W / 64)] holding the 64-bit words of pd_eval.h (pixel q = bit q % 64 of word q / 64)."""
 import ctypes
+from functools import partial
 
 import torch
 
-from .. import lib as _lib
+from .grouped_launch import as_u8, launch, ptr, require_cuda
 
 LIMITS = (1, 10, 50, 100, 200)            # AR@k of the proposal evaluator
 MAX_ROWS, MAX_GT = 200, 64
+_cuda = partial(require_cuda, "pd_eval")
+_launch = partial(launch, table_bytes="pd_eval_table_bytes")
 
 
 class PdEvalMaskSet(ctypes.Structure):
@@ -33,41 +36,8 @@ class PdEvalRecall(ctypes.Structure):
                 ("p", ctypes.c_int32), ("g", ctypes.c_int32)]
 
 
-_RINGS = {}
-
-
 def words_of(hw):
     return (int(hw) + 63) // 64
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def _launch(fn, struct, fields, extra, device, table_bytes="pd_eval_table_bytes"):
-    """fill a host descriptor list, stage it through a pinned ring slot and call fn(list, count, *extra, pinned, device table, stream);
-    table_bytes names the library's size query of the kernel family (functions/pixel_grouping.py stages its tables here too)"""
-    L = _lib.load()
-    arr = (struct * len(fields))()
-    for d, f in zip(arr, fields):
-        for k, v in f.items():
-            setattr(d, k, v)
-    nbytes = int(getattr(L, table_bytes)(len(fields)))
-    cap = 1 << max(8, (nbytes - 1).bit_length())
-    ring = _RINGS.get(cap)
-    if ring is None:
-        from .fused import PinnedRing
-        ring = _RINGS[cap] = PinnedRing(cap, torch.uint8, pin=True)
-    tdev = torch.empty(cap, dtype=torch.uint8, device=device)
-    host = ring.acquire()
-    rc = getattr(L, fn)(arr, len(fields), *extra, host.data_ptr(), tdev.data_ptr(), _lib.current_stream())
-    ring.release()
-    _lib.check(rc)
-
-
-def _cuda(t, what):
-    if not t.is_cuda:
-        raise RuntimeError(f"pd_eval: {what} must be on the GPU (no CPU fallback in partdistillation_amd)")
 
 
 def pack_masks(mask_sets):
@@ -84,14 +54,13 @@ def pack_masks(mask_sets):
         hw = m[0].numel() if n else int(torch.tensor(m.shape[1:]).prod())
         if hw <= 0:
             raise ValueError("pack_masks: empty masks")
-        m = m.contiguous().reshape(n, hw)
-        flat.append(m.view(torch.uint8) if m.dtype == torch.bool else m)
+        flat.append(as_u8(m, "pack_masks").reshape(n, hw))
         layout.append((n, hw, wtot, ntot))
         wtot += n * words_of(hw)
         ntot += n
     bits = torch.empty(max(wtot, 1), dtype=torch.int64, device=dev)
     area = torch.zeros(max(ntot, 1), dtype=torch.int64, device=dev)
-    fields = [dict(masks=_ptr(m), bits=bits.data_ptr() + 8 * wo, area=area.data_ptr() + 8 * no, n=n, hw=hw)
+    fields = [dict(masks=ptr(m), bits=bits.data_ptr() + 8 * wo, area=area.data_ptr() + 8 * no, n=n, hw=hw)
               for m, (n, hw, wo, no) in zip(flat, layout)]
     _launch("pd_eval_pack_grouped", PdEvalMaskSet, fields, (), dev)
     return [(bits[wo:wo + n * words_of(hw)].view(n, words_of(hw)), area[no:no + n]) for n, hw, wo, no in layout]
@@ -117,7 +86,7 @@ def intersections(items):
         layout.append((p, g, tot))
         tot += p * g
     inter = torch.zeros(tot, dtype=torch.int64, device=dev)
-    fields = [dict(a=a.data_ptr(), rows=_ptr(rows), b=b.data_ptr(), inter=inter.data_ptr() + 8 * o, p=p, g=g, words=a.shape[1])
+    fields = [dict(a=a.data_ptr(), rows=ptr(rows), b=b.data_ptr(), inter=inter.data_ptr() + 8 * o, p=p, g=g, words=a.shape[1])
               for (a, rows, b), (p, g, o) in zip(items, layout)]
     _launch("pd_eval_intersect_grouped", PdEvalPairs, fields, (), dev)
     return [inter[o:o + p * g].view(p, g) for p, g, o in layout]
@@ -173,5 +142,5 @@ def recall_add(items, thr, hits, num_pos):
         if not (1 <= p <= MAX_ROWS and 1 <= g <= MAX_GT) or inter.dtype != torch.int64 or not inter.is_contiguous() \
                 or area_g.numel() != g or (rows is not None and rows.numel() != p):
             raise ValueError(f"recall_add: inter int64 [p <= {MAX_ROWS}, g <= {MAX_GT}] with matching rows / areas expected")
-        fields.append(dict(inter=inter.data_ptr(), rows=_ptr(rows), area_p=area_p.data_ptr(), area_g=area_g.data_ptr(), p=p, g=g))
+        fields.append(dict(inter=inter.data_ptr(), rows=ptr(rows), area_p=area_p.data_ptr(), area_g=area_g.data_ptr(), p=p, g=g))
     _launch("pd_eval_recall_grouped", PdEvalRecall, fields, (thr.data_ptr(), hits.data_ptr(), num_pos.data_ptr()), hits.device)

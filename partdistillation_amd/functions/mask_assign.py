@@ -1,13 +1,16 @@
 """Per-pixel mask assignment at a resized output and its histogram on the device (include/pd_assign.h, csrc/mask_assign_resized.hip).
-Each function is ONE launch for all images of a batch (descriptor table staged through the pinned ring of functions/eval_metrics.py)
+Each function is ONE launch for all images of a batch (descriptor table staged through the pinned ring of functions/grouped_launch.py)
 and reads nothing back to the host."""
 import ctypes
+from functools import partial
 
 import torch
 
-from .eval_metrics import _launch
+from .grouped_launch import as_u8, launch, require_cuda
 
 MAX_K, MAX_KEYS, MAX_GT = 256, 1024, 64
+_cuda = partial(require_cuda, "pd_assign")
+_launch = partial(launch, table_bytes="pd_assign_table_bytes")
 
 
 class PdAssignResized(ctypes.Structure):
@@ -18,18 +21,6 @@ class PdAssignResized(ctypes.Structure):
 class PdAssignHistogram(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("key", "obj", "gt", "won", "area", "inter", "gt_area")] + \
         [("n", ctypes.c_int32), ("G", ctypes.c_int32), ("hw", ctypes.c_int64)]
-
-
-def _cuda(t, what):
-    if not t.is_cuda:
-        raise RuntimeError(f"pd_assign: {what} must be on the GPU (no CPU fallback in partdistillation_amd)")
-
-
-def _u8(m, what):
-    if m.dtype not in (torch.bool, torch.uint8):
-        raise ValueError(f"{what}: bool / uint8 expected, got {m.dtype}")
-    m = m.contiguous()
-    return m.view(torch.uint8) if m.dtype == torch.bool else m
 
 
 def mask_assign_resized(items):
@@ -56,7 +47,7 @@ def mask_assign_resized(items):
         o8 = None
         if obj_in is not None:
             _cuda(obj_in, "object mask")
-            o8 = _u8(obj_in, "mask_assign_resized: object mask")
+            o8 = as_u8(obj_in, "mask_assign_resized: object mask")
             if tuple(o8.shape) != (H, W):
                 raise ValueError(f"mask_assign_resized: object mask {tuple(o8.shape)} is not at the output size {(H, W)}")
         if coq is not None:
@@ -74,7 +65,7 @@ def mask_assign_resized(items):
                            positive=positive.data_ptr() + 4 * off, cls=None if cls is None else cls.data_ptr(), K=K, h=h, w=w, Hp=int(Hp),
                            Wp=int(Wp), Hi=int(Hi), Wi=int(Wi), H=H, W=W))
         off += K
-    _launch("pd_mask_assign_resized", PdAssignResized, fields, (), dev, table_bytes="pd_assign_table_bytes")
+    _launch("pd_mask_assign_resized", PdAssignResized, fields, (), dev)
     return out
 
 
@@ -101,13 +92,13 @@ def assign_histogram(items, flat=False):
             raise ValueError(f"assign_histogram: int16 key map [H, W] and an object map of its size expected, got {key.dtype} {tuple(key.shape)}, "
                              f"{tuple(obj.shape)}")
         _cuda(obj, "object map")
-        key, o8 = key.contiguous(), _u8(obj, "assign_histogram: object map")
+        key, o8 = key.contiguous(), as_u8(obj, "assign_histogram: object map")
         g8 = None
         if G:
             _cuda(gt, "gt masks")
             if tuple(gt.shape[1:]) != tuple(key.shape):
                 raise ValueError(f"assign_histogram: gt masks {tuple(gt.shape)} do not match the map {tuple(key.shape)}")
-            g8 = _u8(gt, "assign_histogram: gt masks")
+            g8 = as_u8(gt, "assign_histogram: gt masks")
         keep += [key, o8, g8]
         base = counts.data_ptr() + 8 * o
         won, area = counts[o:o + n], counts[o + n:o + 2 * n]
@@ -115,5 +106,5 @@ def assign_histogram(items, flat=False):
         out.append((won, area, inter, gt_area))
         fields.append(dict(key=key.data_ptr(), obj=o8.data_ptr(), gt=None if g8 is None else g8.data_ptr(), won=base, area=base + 8 * n,
                            inter=base + 16 * n if G else None, gt_area=base + 8 * (2 * n + n * G) if G else None, n=n, G=G, hw=key.numel()))
-    _launch("pd_assign_histogram", PdAssignHistogram, fields, (), dev, table_bytes="pd_assign_table_bytes")
+    _launch("pd_assign_histogram", PdAssignHistogram, fields, (), dev)
     return (out, counts[:tot]) if flat else out

@@ -1,13 +1,16 @@
 """Label maps and boolean masks of resized evaluation images on the device (include/pd_grouping.h, csrc/pixel_grouping.hip).  Each
-function is ONE launch for all images of a batch (descriptor table staged through the pinned ring of functions/eval_metrics.py) and
+function is ONE launch for all images of a batch (descriptor table staged through the pinned ring of functions/grouped_launch.py) and
 reads nothing back to the host."""
 import ctypes
+from functools import partial
 
 import torch
 
-from .eval_metrics import _launch
+from .grouped_launch import as_u8, launch, require_cuda
 
 MAX_K = 32
+_cuda = partial(require_cuda, "pd_grouping")
+_launch = partial(launch, table_bytes="pd_grouping_table_bytes")
 
 
 class PdGroupLabels(ctypes.Structure):
@@ -18,18 +21,6 @@ class PdGroupLabels(ctypes.Structure):
 class PdMaskResize(ctypes.Structure):
     _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("area", ctypes.c_void_p)] + \
         [(k, ctypes.c_int32) for k in ("n", "Hp", "Wp", "Hi", "Wi", "H", "W", "reserved")]
-
-
-def _cuda(t, what):
-    if not t.is_cuda:
-        raise RuntimeError(f"pd_grouping: {what} must be on the GPU (no CPU fallback in partdistillation_amd)")
-
-
-def _u8(m, what):
-    if m.dtype not in (torch.bool, torch.uint8):
-        raise ValueError(f"{what}: bool / uint8 expected, got {m.dtype}")
-    m = m.contiguous()
-    return m.view(torch.uint8) if m.dtype == torch.bool else m
 
 
 def scores_argmax_resized(items):
@@ -49,14 +40,14 @@ def scores_argmax_resized(items):
         if s.dtype != torch.float32 or s.dim() != 3 or not 1 <= s.shape[0] <= MAX_K or m.dim() != 2:
             raise ValueError(f"scores_argmax_resized: fp32 scores [K <= {MAX_K}, h, w] and a mask [H, W] expected, got {s.dtype} {tuple(s.shape)}, "
                              f"{tuple(m.shape)}")
-        s, m8 = s.contiguous(), _u8(m, "scores_argmax_resized: mask")
+        s, m8 = s.contiguous(), as_u8(m, "scores_argmax_resized: mask")
         H, W = m8.shape
         out = torch.empty((H, W), dtype=torch.uint8, device=dev)
         keep += [s, m8]
         labels.append(out)
         fields.append(dict(scores=s.data_ptr(), mask=m8.data_ptr(), labels=out.data_ptr(), counts=counts[b].data_ptr(), K=s.shape[0],
                            h=s.shape[1], w=s.shape[2], Hp=int(Hp), Wp=int(Wp), Hi=int(Hi), Wi=int(Wi), H=H, W=W))
-    _launch("pd_scores_argmax_resized_u8", PdGroupLabels, fields, (), dev, table_bytes="pd_grouping_table_bytes")
+    _launch("pd_scores_argmax_resized_u8", PdGroupLabels, fields, (), dev)
     return labels, counts
 
 
@@ -75,7 +66,7 @@ def masks_resize(items):
     for m, (Hi, Wi), (H, W) in items:
         if m.dim() != 3:
             raise ValueError(f"masks_resize: masks [n, Hp, Wp] expected, got {tuple(m.shape)}")
-        m8 = _u8(m, "masks_resize: masks")
+        m8 = as_u8(m, "masks_resize: masks")
         n, Hp, Wp = m8.shape
         dst = torch.empty((n, int(H), int(W)), dtype=torch.uint8, device=dev)
         keep.append(m8)
@@ -83,5 +74,5 @@ def masks_resize(items):
         fields.append(dict(src=m8.data_ptr() if n else None, dst=dst.data_ptr() if n else None, area=area.data_ptr() + 8 * off, n=n, Hp=Hp, Wp=Wp,
                            Hi=int(Hi), Wi=int(Wi), H=int(H), W=int(W)))
         off += n
-    _launch("pd_masks_resize_u8", PdMaskResize, fields, (), dev, table_bytes="pd_grouping_table_bytes")
+    _launch("pd_masks_resize_u8", PdMaskResize, fields, (), dev)
     return out
