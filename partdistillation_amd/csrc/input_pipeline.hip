@@ -73,13 +73,7 @@ __global__ __launch_bounds__(256) void rle_sample(const int32_t *__restrict__ st
   if (x < S && y < vh && x < vw) {
     const int sx = flip ? W - 1 - src_x[x] : src_x[x];
     const int pos = sx * H + src_y[y];
-    const int32_t *st = starts + offsets[i];
-    int lo = 0, hi = offsets[i + 1] - offsets[i];          // last run whose start <= pos
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (st[mid] <= pos) lo = mid; else hi = mid;
-    }
-    v = lo & 1;                                             // runs alternate 0, 1, 0, ... starting with zeros
+    v = pd_rle_find_run(starts + offsets[i], offsets[i + 1] - offsets[i], pos) & 1;
   }
   if (x < S) out[((int64_t)i * S + y) * S + x] = (uint8_t)v;
   const unsigned long long ball = __ballot(v != 0);

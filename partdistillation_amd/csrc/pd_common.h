@@ -2,6 +2,7 @@
 #ifndef PD_COMMON_H
 #define PD_COMMON_H
 #include <hip/hip_runtime.h>
+#include <stdint.h>
 
 // Records a printf-style message for pd_last_error() and returns `code`.
 int pd_set_error(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
@@ -23,6 +24,18 @@ __device__ __forceinline__ T *pd_as_global(T *p)
   G g = (G)p;
   asm("" : "+s"(g));
   return (T *)g;
+}
+
+// Index of the last run whose start is <= pos, in a mask's `count` ascending run starts (pd_input.h's format: st[0] = 0); 0 for an empty list.
+// The runs alternate 0, 1, 0, ... starting with zeros, so the pixel's value is the parity of the result.
+__device__ __forceinline__ int pd_rle_find_run(const int32_t *__restrict__ st, int count, int pos)
+{
+  int lo = 0, hi = count;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (st[mid] <= pos) lo = mid; else hi = mid;
+  }
+  return lo;
 }
 #endif
 #endif

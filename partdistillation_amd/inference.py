@@ -395,26 +395,36 @@ def _save_dict(root, inp, res):
 def save_generated_part_labels(model, inp, label, instance):
     """reference part_ranking_model.py:262-279: one torch.save-d dict per image under root_save_path/class_code/image_id —
     the on-disk pseudo-label format the part-distillation dataset reads (COCO RLE dicts with utf-8 counts)."""
-    from .utils import rle
-    masks = instance.pred_masks.cpu()
-    H, W = masks.shape[1:]
+    part_masks, areas = _encode_pred_masks(instance.pred_masks)
+    H, W = instance.pred_masks.shape[1:]
     res = {"file_name": inp["file_name"], "image_id": inp["image_id"], "class_code": inp["class_code"], "height": H, "width": W,
-           "part_masks": rle.masks_to_coco_json(masks), "part_labels": instance.pred_classes.cpu(),
-           "object_ratio": masks.sum().long().item() / (H * W), "part_ratios": masks.flatten(1).sum(-1) / (H * W),
+           "part_masks": part_masks, "part_labels": instance.pred_classes.cpu(),
+           "object_ratio": areas.sum().long().item() / (H * W), "part_ratios": areas / (H * W),
            "object_class_label": int(label), "part_scores": instance.scores.cpu().numpy()}
     _save_dict(model.root_save_path, inp, res)
     return res
 
 
+def _encode_pred_masks(pred_masks):
+    """bool [n, H, W] -> (the reference's proposals_to_coco_json(masks), every mask's pixel count int64 [n] on the CPU).  Masks on the GPU go
+    through the device codec (functions/rle.py): run tables and exact counts cross the bus, no dense mask does."""
+    from .utils import rle
+    if pred_masks.is_cuda and pred_masks.dtype == torch.bool:
+        from .functions import rle as device_rle
+        part_masks, areas = device_rle.encode_masks(pred_masks)
+        return part_masks, torch.from_numpy(areas)
+    masks = pred_masks.cpu()
+    return rle.masks_to_coco_json(masks), masks.flatten(1).sum(-1)
+
+
 def save_part_segmentation(model, inp, instance):
     """reference part_distillation_model.py:290-307"""
-    from .utils import rle
-    masks = instance.pred_masks.cpu()
-    H, W = masks.shape[1:]
-    object_area = masks.sum().long().item()
+    part_masks, areas = _encode_pred_masks(instance.pred_masks)
+    H, W = instance.pred_masks.shape[1:]
+    object_area = areas.sum().long().item()
     res = {"file_name": inp["file_name"], "image_id": inp["image_id"], "class_code": inp["class_code"], "height": H, "width": W,
-           "part_masks": rle.masks_to_coco_json(masks), "part_labels": instance.pred_classes.cpu(),
-           "part_area_ratios": masks.flatten(1).sum(-1).long() / object_area, "object_ratio": object_area / (H * W),
+           "part_masks": part_masks, "part_labels": instance.pred_classes.cpu(),
+           "part_area_ratios": areas.long() / object_area, "object_ratio": object_area / (H * W),
            "part_scores": instance.scores.cpu().numpy()}
     _save_dict(model.root_save_path, inp, res)
     return res

@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("PD_LIB_PATH") or os.path.join(_HERE, "libpd_hip.so") 
 CSRC = os.path.join(_HERE, "csrc")
 
 PD_F32, PD_F64, PD_BF16 = 0, 1, 2
-ABI_VERSION = 42
+ABI_VERSION = 43
 
 _c_int, _c_vp = ctypes.c_int, ctypes.c_void_p
 
@@ -218,6 +218,11 @@ SIGNATURES = {
     "pd_dcrf_spatial_message": (_c_int, [_c_vp, _c_vp] + [_c_int] * 3 + [ctypes.c_double] * 2 + [_c_vp] * 3),
     "pd_dcrf_bilateral_update": (_c_int, [_c_vp] * 5 + [_c_int] * 3 + [ctypes.c_double] * 4 + [_c_vp, _c_vp]),
     "pd_dcrf_argmax": (_c_int, [_c_vp] + [_c_int] * 3 + [_c_vp, _c_vp]),
+    # include/pd_rle.h
+    "pd_rle_seg_rows": (_c_int, []),
+    "pd_rle_runs_workspace_bytes": (ctypes.c_int64, [_c_int] * 3),
+    "pd_rle_plane_runs": (_c_int, [_c_vp, ctypes.c_int64] + [_c_int] * 5 + [_c_vp] * 6),
+    "pd_rle_decode": (_c_int, [_c_vp, _c_vp] + [_c_int] * 3 + [_c_vp, _c_vp, _c_vp]),
     "pd_cmd_fn_index": (_c_int, [ctypes.c_char_p]),
     "pd_cmd_fn_nargs": (_c_int, [_c_int]),
     "pd_cmd_replay": (_c_int, [_c_vp, _c_int, _c_vp, _c_int, _c_vp]),

@@ -27,6 +27,15 @@ def refine_proposals(data, image, size=640, device="cuda", **crf):
     key = next((k for k in MASK_KEYS if k in data), None)
     if key is None or data[key] is None or len(data[key]) == 0:
         return data
+    if torch.device(device).type == "cuda":
+        # the masks stay run tables on the bus: strings -> run starts (host) -> label map (device) -> dense_crf -> run table -> strings
+        from .functions import rle as device_rle
+        num_c = len(data[key])
+        cmask = device_rle.decode_label_map(data[key], (size, size), device)         # ValueError "... do not match ..." on another size
+        img = resize_image(image, size, device)
+        out = _dcrf.dense_crf(img, cmask, num_c + 1, **crf)
+        data[key], _ = device_rle.encode_label_map(out)                               # one mask per non-zero label that survives
+        return data
     bmask = np.stack([rle.decode(m["segmentation"]) for m in data[key]])
     if tuple(bmask.shape[1:]) != (size, size):
         raise ValueError(f"tensor shapes do not match. ({(size, size)} != {tuple(bmask.shape[1:])})")

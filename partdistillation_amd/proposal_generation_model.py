@@ -13,12 +13,14 @@ Same class name / registry / config keys / result dictionary as the reference.  
 import os
 from typing import List, Tuple
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 from torch import nn
 
 from . import lib as _lib
 from .compat import META_ARCH_REGISTRY, ImageList, build_backbone, configurable
+from .functions import rle as device_rle
 from .functions.kmeans import kmeans_lloyd_batched
 from .utils import rle
 
@@ -152,16 +154,13 @@ class ProposalGenerationModel(nn.Module):
 
     def _result(self, inp, labels, object_mask, centroids, n_iter):
         H, W = labels.shape
-        counts = torch.bincount(labels.flatten().long(), minlength=self.num_superpixel_clusters + 1)
-        # run-length form of the column-major label map on the device; only the run table crosses to the host — in ONE copy with the label
-        # counts and the object's area (was five blocking reads per image)
-        flat = labels.t().contiguous().flatten()
-        starts = torch.cat([flat.new_zeros(1, dtype=torch.long), (flat[1:] != flat[:-1]).nonzero().flatten() + 1])
-        lengths = torch.diff(starts, append=starts.new_tensor([flat.numel()]))
-        packed = torch.cat([counts, object_mask.sum().reshape(1), flat[starts].long(), lengths]).cpu().numpy()
-        nk = counts.numel()
-        counts_h, area, runs = packed[:nk].tolist(), int(packed[nk]), packed[nk + 1:]
-        values, lengths = runs[:runs.size // 2].astype("uint8"), runs[runs.size // 2:]
+        # run-length form of the column-major label map from the device codec (functions/rle.py): only the run table crosses to the host.  The
+        # per-label pixel counts are sums of run lengths; the object's area is the map's non-zero count (labels are 1 + arg-max exactly on the
+        # object's pixels, _label_map)
+        _, starts, values, nonzero = device_rle.plane_runs(labels[None], binary=False)
+        lengths = np.diff(starts.astype(np.int64), append=H * W)
+        counts_h = device_rle.label_counts(values, lengths, self.num_superpixel_clusters + 1).tolist()
+        area = int(nonzero[0])
         present = [l for l in range(1, len(counts_h)) if counts_h[l] > 0]
         res = {"file_name": inp.get("file_name"), "file_path": inp.get("file_path"), "class_code": inp.get("class_code"),
                "class_name": inp.get("class_name"), "part_mask": rle.runs_to_coco_json(values, lengths, (H, W), present),

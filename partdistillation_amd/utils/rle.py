@@ -44,23 +44,26 @@ def counts_to_string(counts) -> bytes:
 
 
 def string_to_counts(s) -> np.ndarray:
+    """vectorised rleFrString: every count's 5-bit groups are summed with one reduceat (their bits are disjoint), the sign bit of the last
+    group extends it, and the `x += cnts[-2]` recurrence (from the fourth count on) is a cumulative sum over the odd indices from 1 and
+    one over the even indices from 2."""
     if isinstance(s, str):
         s = s.encode("ascii")
-    cnts, p = [], 0
-    while p < len(s):
-        x, k, more = 0, 0, True
-        while more:
-            c = s[p] - 48
-            x |= (c & 0x1F) << (5 * k)
-            more = bool(c & 0x20)
-            p += 1
-            k += 1
-            if not more and (c & 0x10):
-                x |= -1 << (5 * k)
-        if len(cnts) > 2:
-            x += cnts[-2]
-        cnts.append(x)
-    return np.asarray(cnts, dtype=np.int64)
+    c = np.frombuffer(bytes(s), dtype=np.uint8).astype(np.int64) - 48
+    if c.size == 0:
+        return np.zeros((0,), dtype=np.int64)
+    more = (c & 0x20) != 0
+    if more[-1]:
+        raise IndexError("string_to_counts: the string ends inside a count")
+    last = np.flatnonzero(~more)                                       # last character of every count
+    first = np.concatenate(([0], last[:-1] + 1))
+    groups = last - first + 1
+    k = np.arange(c.size) - np.repeat(first, groups)                   # group index inside its count
+    x = np.add.reduceat((c & 0x1F) << np.minimum(5 * k, 63), first)
+    x = np.where((c[last] & 0x10) != 0, x | (np.int64(-1) << np.minimum(5 * groups, 63)), x)
+    x[1::2] = np.cumsum(x[1::2])
+    x[2::2] = np.cumsum(x[2::2])
+    return x
 
 
 def encode(mask: np.ndarray) -> dict:
@@ -123,3 +126,35 @@ def masks_to_coco_json(masks) -> list:
         out.append({"segmentation": r})
     return out
 
+
+def run_table_to_coco_json(offsets, starts, values, size) -> list:
+    """masks_to_coco_json from the run tables of the masks (functions.rle.plane_runs(..., binary=True)): mask i's runs are the entries
+    [offsets[i], offsets[i + 1]) of starts (ascending positions in the column-major flattening, the first 0) and values (0 / 1,
+    alternating).  A mask whose first run is ones gets COCO's leading zero count."""
+    h, w = int(size[0]), int(size[1])
+    offsets, starts, values = np.asarray(offsets), np.asarray(starts, dtype=np.int64), np.asarray(values)
+    out = []
+    for i in range(len(offsets) - 1):
+        a, b = int(offsets[i]), int(offsets[i + 1])
+        counts = np.diff(starts[a:b], append=h * w)
+        if b > a and values[a]:
+            counts = np.concatenate(([0], counts))
+        out.append({"segmentation": {"size": [h, w], "counts": counts_to_string(counts).decode("utf-8")}})
+    return out
+
+
+def segmentations_to_starts(segmentations, size):
+    """list[COCO RLE dict] (counts as str / bytes / run lengths) -> (starts, offsets) int32, pd_rle_sample_u8's format: for mask i the
+    entries [offsets[i], offsets[i + 1]) of starts are the exclusive prefix sums of its run lengths.  ValueError when a mask's size differs
+    from `size`."""
+    size = (int(size[0]), int(size[1]))
+    starts, offsets = [np.zeros((0,), dtype=np.int32)], [0]
+    for seg in segmentations:
+        if tuple(int(v) for v in seg["size"]) != size:
+            raise ValueError(f"tensor shapes do not match. ({size} != {tuple(int(v) for v in seg['size'])})")
+        counts = seg["counts"]
+        counts = string_to_counts(counts) if isinstance(counts, (str, bytes)) else np.asarray(counts, dtype=np.int64)
+        cs = np.concatenate(([0], np.cumsum(counts[:-1]))) if len(counts) else np.zeros(1)
+        starts.append(cs.astype(np.int32))
+        offsets.append(offsets[-1] + len(cs))
+    return np.concatenate(starts), np.asarray(offsets, dtype=np.int32)
