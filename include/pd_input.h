@@ -14,6 +14,13 @@
  *                         col(j) = x0 + j, mirrored (W - 1 - col) when `flip` — flip and first crop are just addressing
  *   pd_resample_cols_u8   vertical pass + second crop + pad + HWC -> CHW:
  *                         out[c][y][x] = y < vh && x < vw ? clip8((2^21 + sum_k tmp[ymin[y] + k - r0][x][c] * kk[y][k]) >> 22) : pad
+ *   pd_resample_cols_canvas_u8   the same vertical pass onto a RECTANGULAR out_h x out_w canvas, interleaved or planar: the base
+ *                         resize of the mappers (ResizeScale(1, 1, base, base) [+ FixedSizeCrop((base, base))] ahead of the augmentations).
+ *                         planar = 0: out[y][x][c], the HWC layout pd_resample_rows_u8 reads, so the base image feeds the next resize
+ *                         as it is; planar = 1: out[c][y][x].  Same arithmetic, y >= vh or x >= vw take pad_value.  A canvas has at
+ *                         least one pixel and sides of at most PD_CANVAS_MAX_SIDE (anything else is PD_ERR_INVALID_ARG, as are
+ *                         vh > out_h, vw > out_w, vw > tmp_w, ksize <= 0 and a null pointer that would be read or written), so there is
+ *                         no empty request: vh = 0 or vw = 0 launches and fills the canvas with pad_value
  *   pd_rle_sample_u8      all masks of the image, straight from their run lengths (no dense full-resolution mask):
  *                         out[i][y][x] = inside ? parity(search(starts_i, colmajor(src_x[x], src_y[y]))) : 0, and
  *                         area[i] += popcount — src_x / src_y = the composed nearest-neighbour index tables
@@ -36,6 +43,11 @@ int pd_resample_rows_u8(const uint8_t *src, int H, int W, int row0, int rows, in
 
 int pd_resample_cols_u8(const uint8_t *tmp, int tmp_rows, int tmp_w, int r0, const int32_t *ymin, const int32_t *cnt,
                         const int32_t *kk, int ksize, int vh, int vw, int S, int pad_value, uint8_t *out, void *stream);
+
+#define PD_CANVAS_MAX_SIDE 65535
+int pd_resample_cols_canvas_u8(const uint8_t *tmp, int tmp_rows, int tmp_w, int r0, const int32_t *ymin, const int32_t *cnt,
+                               const int32_t *kk, int ksize, int vh, int vw, int out_h, int out_w, int pad_value, int planar,
+                               uint8_t *out, void *stream);
 
 int pd_rle_sample_u8(const int32_t *starts, const int32_t *offsets, int n_masks, int H, int W, int flip, const int32_t *src_x,
                      const int32_t *src_y, int vh, int vw, int S, uint8_t *out, int32_t *area, void *stream);

@@ -1,5 +1,6 @@
 // Device input pipeline (include/pd_input.h): Pillow-exact 8-bit bilinear resample in two passes with flip / crops / pad
-// folded into the addressing, and mask sampling straight from COCO run lengths.  All three kernels are byte streams
+// folded into the addressing (onto the square training canvas, or a rectangular base canvas), and mask sampling straight from COCO run
+// lengths.  All of these kernels are byte streams
 // (HBM-bound at a few MB per image); the point is to take ~10 ms of per-image CPU work off the dataloader.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -38,13 +39,13 @@ __global__ __launch_bounds__(256) void resample_rows(const uint8_t *__restrict__
   o[0] = clip8(a0); o[1] = clip8(a1); o[2] = clip8(a2);
 }
 
-// one thread per output pixel of the S x S canvas, all 3 channel planes
+// one thread per output pixel of the out_h x out_w canvas (S x S for pd_resample_cols_u8), all 3 channel planes
 __global__ __launch_bounds__(256) void resample_cols(const uint8_t *__restrict__ tmp, int tmp_w, int r0, const int32_t *__restrict__ ymin,
                                                      const int32_t *__restrict__ cnt, const int32_t *__restrict__ kk, int ksize, int vh,
-                                                     int vw, int S, int pad_value, uint8_t *__restrict__ out)
+                                                     int vw, int out_h, int out_w, int pad_value, uint8_t *__restrict__ out)
 {
   const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-  if (x >= S) return;
+  if (x >= out_w) return;
   int a0, a1, a2;
   if (y < vh && x < vw) {
     const int32_t *k = kk + (int64_t)y * ksize;
@@ -59,8 +60,27 @@ __global__ __launch_bounds__(256) void resample_cols(const uint8_t *__restrict__
   } else {
     a0 = a1 = a2 = pad_value;
   }
-  const int64_t plane = (int64_t)S * S, o = (int64_t)y * S + x;
+  const int64_t plane = (int64_t)out_h * out_w, o = (int64_t)y * out_w + x;
   out[o] = (uint8_t)a0; out[plane + o] = (uint8_t)a1; out[2 * plane + o] = (uint8_t)a2;
+}
+
+// the same pass onto an interleaved [out_h, out_w, 3] canvas, one thread per BYTE of a canvas row: a tmp row has the same pixel-major,
+// channel-minor order, so byte e of the row is tapped at byte e of the tmp rows — every tap is 64 consecutive bytes per wave, and so is the store
+__global__ __launch_bounds__(256) void resample_cols_hwc(const uint8_t *__restrict__ tmp, int tmp_w, int r0, const int32_t *__restrict__ ymin,
+                                                         const int32_t *__restrict__ cnt, const int32_t *__restrict__ kk, int ksize, int vh,
+                                                         int vw, int out_w, int pad_value, uint8_t *__restrict__ out)
+{
+  const int e = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+  if (e >= out_w * 3) return;
+  int a = pad_value;
+  if (y < vh && e < vw * 3) {
+    const int32_t *k = kk + (int64_t)y * ksize;
+    const int first = ymin[y] - r0, n = cnt[y];
+    a = 1 << (PRECISION_BITS - 1);
+    for (int j = 0; j < n; ++j) a += tmp[(int64_t)(first + j) * tmp_w * 3 + e] * k[j];
+    a = clip8(a);
+  }
+  out[(int64_t)y * out_w * 3 + e] = (uint8_t)a;
 }
 
 // one thread per (mask, output pixel): binary search of the pixel's column-major position in the mask's run starts
@@ -100,8 +120,27 @@ extern "C" int pd_resample_cols_u8(const uint8_t *tmp, int tmp_rows, int tmp_w, 
     return pd_set_error(PD_ERR_INVALID_ARG, "pd_resample_cols_u8: bad sizes S=%d vh=%d vw=%d tmp_w=%d", S, vh, vw, tmp_w);
   if (!out || (vh > 0 && vw > 0 && (!tmp || !ymin || !cnt || !kk))) return pd_set_error(PD_ERR_INVALID_ARG, "pd_resample_cols_u8: null pointer");
   hipLaunchKernelGGL(resample_cols, dim3((S + 255) / 256, S), dim3(256), 0, (hipStream_t)stream_, tmp, tmp_w, r0, ymin, cnt, kk, ksize,
-                     vh, vw, S, pad_value, out);
+                     vh, vw, S, S, pad_value, out);
   return pd_check_launch("pd_resample_cols_u8");
+}
+
+extern "C" int pd_resample_cols_canvas_u8(const uint8_t *tmp, int tmp_rows, int tmp_w, int r0, const int32_t *ymin, const int32_t *cnt,
+                                          const int32_t *kk, int ksize, int vh, int vw, int out_h, int out_w, int pad_value, int planar,
+                                          uint8_t *out, void *stream_)
+{
+  if (out_h <= 0 || out_w <= 0 || out_h > PD_CANVAS_MAX_SIDE || out_w > PD_CANVAS_MAX_SIDE || vh < 0 || vw < 0 || vh > out_h || vw > out_w ||
+      vw > tmp_w || ksize <= 0)
+    return pd_set_error(PD_ERR_INVALID_ARG, "pd_resample_cols_canvas_u8: bad sizes canvas=%dx%d (sides 1..%d) vh=%d vw=%d tmp_w=%d ksize=%d", out_h,
+                        out_w, PD_CANVAS_MAX_SIDE, vh, vw, tmp_w, ksize);
+  if (!out || (vh > 0 && vw > 0 && (!tmp || !ymin || !cnt || !kk)))
+    return pd_set_error(PD_ERR_INVALID_ARG, "pd_resample_cols_canvas_u8: null pointer");
+  if (planar)
+    hipLaunchKernelGGL(resample_cols, dim3((out_w + 255) / 256, out_h), dim3(256), 0, (hipStream_t)stream_, tmp, tmp_w, r0, ymin, cnt, kk,
+                       ksize, vh, vw, out_h, out_w, pad_value, out);
+  else
+    hipLaunchKernelGGL(resample_cols_hwc, dim3((out_w * 3 + 255) / 256, out_h), dim3(256), 0, (hipStream_t)stream_, tmp, tmp_w, r0, ymin, cnt,
+                       kk, ksize, vh, vw, out_w, pad_value, out);
+  return pd_check_launch("pd_resample_cols_canvas_u8");
 }
 
 extern "C" int pd_rle_sample_u8(const int32_t *starts, const int32_t *offsets, int n_masks, int H, int W, int flip, const int32_t *src_x,

@@ -1,1 +1,1 @@
-from .device_mapper import DeviceProposalMapper  # noqa: F401
+from .device_mapper import DevicePartDistillationMapper, DeviceProposalMapper  # noqa: F401

@@ -8,8 +8,20 @@ Device side: the Pillow-exact two-pass bilinear resample of the image with flip 
 and every pseudo-label mask sampled straight from its run lengths (decode + flip + crop + nearest resize + crop + pad in
 one kernel, no dense full-resolution mask), plus the mask areas for the reference's area-ratio filter (:225-235).
 The uploaded image is the decoded uint8 HWC array; the result is what the reference's mapper returns
-({"image" [3,S,S] uint8, "padding_mask", "instances" (gt_masks BitMasks, gt_classes), "height", "width"}), on the device."""
+({"image" [3,S,S] uint8, "padding_mask", "instances" (gt_masks BitMasks, gt_classes), "height", "width"}), on the device.
+
+Base stage (`base_size > 0`, reference :54-60 and :174-175; CUSTOM_DATASETS.BASE_SIZE 640 in every shipped training script): the image is
+first resized so that its longer side is `base_size` — the resolution the pseudo-labels were generated at — and, for the part-distillation
+mapper with PART_DISTILLATION.SET_IMAGE_SQUARE, padded right / bottom with 128 to base x base.  Pillow rounds to 8 bits after every pass,
+so the base resize cannot be folded into the augmentation's resize: it is its own two passes (pd_resample_rows_u8, then
+pd_resample_cols_canvas_u8 writing the HWC canvas the next pd_resample_rows_u8 reads), done once per image, not once per attempt.
+
+``DevicePartDistillationMapper`` is the same for the reference's PartDistillationDatasetMapper
+(data/dataset_mappers/part_distillation_dataset_mapper.py), train and test; both mappers read the saved pseudo-label dicts of the
+PATH_ONLY datasets through `load_annotation`."""
+import logging
 import math
+import os
 
 import numpy as np
 import torch
@@ -56,28 +68,74 @@ def nearest_index(in_size, out_size):
 
 class DeviceProposalMapper:
     def __init__(self, image_size, min_scale=0.1, max_scale=2.0, crop_type=None, crop_size=None, flip=True, min_area_ratio=0.0,
-                 min_object_area_ratio=0.0, device="cuda", rng=None, pad_value=128, num_repeats=100):
+                 min_object_area_ratio=0.0, device="cuda", rng=None, pad_value=128, num_repeats=100, base_size=-1, square_base=False,
+                 class_code_to_class_id=None):
         self.image_size, self.min_scale, self.max_scale = int(image_size), float(min_scale), float(max_scale)
         self.crop_type, self.crop_size, self.flip = crop_type, crop_size, flip
         self.min_area_ratio, self.min_object_area_ratio = min_area_ratio, min_object_area_ratio
         self.device, self.pad_value, self.num_repeats = torch.device(device), int(pad_value), num_repeats
         self.rng = rng if rng is not None else np.random                 # detectron2 draws from the global numpy RNG
+        self.base_size, self.square_base = int(base_size), bool(square_base)
+        self.class_code_to_class_id = class_code_to_class_id if class_code_to_class_id is not None else {}   # no MetadataCatalog here
+        self.logger = logging.getLogger("part_distillation")
 
-    @classmethod
-    def from_config(cls, cfg, is_train=True, device=None):
+    @staticmethod
+    def _augmentation_args(cfg):
+        """the AUG_NAME_LIST / INPUT.* keys both mappers read (reference :62-97) -> the first six constructor arguments"""
         names = list(cfg.CUSTOM_DATASETS.AUG_NAME_LIST)
         for n in names:
             if n not in ("flip", "crop", "scale"):
                 raise NotImplementedError(f"augmentation '{n}' (reference :68-72: colour jitter / rotation) is not in the device pipeline")
         scale = "scale" in names
-        return cls(cfg.INPUT.IMAGE_SIZE, cfg.INPUT.MIN_SCALE if scale else 1.0, cfg.INPUT.MAX_SCALE if scale else 1.0,
-                   cfg.INPUT.CROP.TYPE if "crop" in names else None, tuple(cfg.INPUT.CROP.SIZE) if "crop" in names else None,
-                   "flip" in names, cfg.PROPOSAL_LEARNING.MIN_AREA_RATIO, cfg.PROPOSAL_LEARNING.MIN_OBJECT_AREA_RATIO,
-                   device or cfg.MODEL.DEVICE)
+        return (cfg.INPUT.IMAGE_SIZE, cfg.INPUT.MIN_SCALE if scale else 1.0, cfg.INPUT.MAX_SCALE if scale else 1.0,
+                cfg.INPUT.CROP.TYPE if "crop" in names else None, tuple(cfg.INPUT.CROP.SIZE) if "crop" in names else None, "flip" in names)
+
+    @classmethod
+    def from_config(cls, cfg, is_train=True, device=None, base_size=-1, class_code_to_class_id=None):
+        """reference :49-60: the caller passes cfg.CUSTOM_DATASETS.BASE_SIZE as `base_size` (part_proposal_train_net.py:73)"""
+        return cls(*cls._augmentation_args(cfg), cfg.PROPOSAL_LEARNING.MIN_AREA_RATIO, cfg.PROPOSAL_LEARNING.MIN_OBJECT_AREA_RATIO,
+                   device or cfg.MODEL.DEVICE, base_size=base_size, class_code_to_class_id=class_code_to_class_id)
+
+    # ------------------------------------------------------------------ host: saved pseudo-labels of the PATH_ONLY datasets
+    def _load_saved(self, path_tuple):
+        """torch.load of dataset_path/class_code/file on the CPU; None (logged) when the file is corrupted"""
+        path = os.path.join(*path_tuple)
+        try:
+            return torch.load(path, map_location="cpu", weights_only=False)      # the dicts hold numpy arrays (part_scores)
+        except OSError:
+            raise                                                                # a missing or unreadable file is not a corrupted one
+        except Exception:
+            self.logger.info("%s is corrupted.", path)
+            return None
+
+    def load_annotation(self, path_tuple):
+        """reference :113-139: the dict ProposalGenerationModel._result saves -> dataset dict, or None when the file is corrupted, the
+        object is not larger than min_object_area_ratio of the image, or there are no part masks"""
+        ann = self._load_saved(path_tuple)
+        if ann is None or not ann["object_ratio"] > self.min_object_area_ratio or not ann["part_mask"]:
+            return None
+        h, w = ann["part_mask"][-1]["segmentation"]["size"]
+        return {"file_name": ann["file_path"], "image_id": ann["file_name"], "class_code": path_tuple[1], "height": h, "width": w,
+                "pseudo_annotations": [{"segmentation": m["segmentation"], "category_id": 0} for m in ann["part_mask"]],   # class-agnostic
+                "gt_object_class": self.class_code_to_class_id[ann["class_code"]]}
 
     # ------------------------------------------------------------------ host: parameter draws (detectron2 0.6 augmentation_impl.py)
+    def base_canvas(self, h, w):
+        """ResizeScale(1.0, 1.0, base, base) [+ FixedSizeCrop((base, base))] of an h x w image -> ((bh, bw) resized, (ch, cw) canvas)"""
+        base = self.base_size
+        scale = min(base * 1.0 / h, base * 1.0 / w)
+        bh, bw = int(np.round(h * scale)), int(np.round(w * scale))
+        return (bh, bw), ((base, base) if self.square_base else (bh, bw))
+
     def draw(self, in_h, in_w, weak=False):
+        """in_h, in_w: the size the augmentations see — the base canvas when the base stage is on"""
         rng, S = self.rng, self.image_size
+        if self.base_size > 0:
+            # the reference applies base_aug inside every _forward (:174-175): its ResizeScale draws its scale, uniform(1.0, 1.0), and
+            # its FixedSizeCrop its offset fraction, uniform(0.0, 1.0) (times a zero range), ahead of the augmentations' own draws
+            rng.uniform(1.0, 1.0)
+            if self.square_base:
+                rng.uniform(0.0, 1.0)
         p = {"in_h": in_h, "in_w": in_w, "size": S, "flip": bool(self.flip and rng.uniform() < 0.5)}
         h, w = in_h, in_w
         p["crop1"] = (0, 0, w, h)
@@ -108,16 +166,39 @@ class DeviceProposalMapper:
     def _dev(self, a):
         return torch.from_numpy(np.ascontiguousarray(a)).to(self.device, non_blocking=True)
 
+    def _upload(self, image):
+        if self.device.type != "cuda":
+            raise RuntimeError("the device input pipeline runs on the GPU only (no CPU fallback in partdistillation_amd)")
+        img = image if torch.is_tensor(image) else torch.from_numpy(np.ascontiguousarray(image))
+        assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3, img.shape
+        return img.to(self.device, non_blocking=True).contiguous()
+
+    def base_image(self, image, planar=False):
+        """image uint8 [H, W, 3] -> the base canvas uint8 [ch, cw, 3] ([3, ch, cw] when `planar`) on the device: Pillow BILINEAR resize
+        to base_canvas(H, W), the rest of the canvas = pad_value"""
+        assert self.base_size > 0, "base_image needs base_size > 0"
+        img = self._upload(image)
+        L, st = _lib.load(), _lib.current_stream()
+        H, W = int(img.shape[0]), int(img.shape[1])
+        (bh, bw), (ch, cw) = self.base_canvas(H, W)
+        ymin, ycnt, ykk = resample_coeffs(H, bh, 0, bh)
+        xmin, xcnt, xkk = resample_coeffs(W, bw, 0, bw)
+        r0, r1 = int(ymin.min()), int((ymin + ycnt).max())
+        tmp = torch.empty((r1 - r0, bw, 3), dtype=torch.uint8, device=self.device)
+        out = torch.empty((3, ch, cw) if planar else (ch, cw, 3), dtype=torch.uint8, device=self.device)
+        tabs = [self._dev(t) for t in (xmin, xcnt, xkk, ymin, ycnt, ykk)]
+        _lib.check(L.pd_resample_rows_u8(img.data_ptr(), H, W, r0, r1 - r0, 0, 0, tabs[0].data_ptr(), tabs[1].data_ptr(), tabs[2].data_ptr(),
+                                         xkk.shape[1], bw, tmp.data_ptr(), st))
+        _lib.check(L.pd_resample_cols_canvas_u8(tmp.data_ptr(), r1 - r0, bw, r0, tabs[3].data_ptr(), tabs[4].data_ptr(), tabs[5].data_ptr(),
+                                                ykk.shape[1], bh, bw, ch, cw, self.pad_value, int(planar), out.data_ptr(), st))
+        return out
+
     def transform(self, image, segmentations, p):
         """image uint8 [H, W, 3] (numpy or tensor), segmentations = list of COCO RLE dicts {"size": [H, W], "counts": str}
         -> (image uint8 [3,S,S], masks bool [n,S,S], padding_mask bool [S,S], areas int32 [n]) on the device"""
-        if self.device.type != "cuda":
-            raise RuntimeError("the device input pipeline runs on the GPU only (no CPU fallback in partdistillation_amd)")
+        img = self._upload(image)
         L, S = _lib.load(), p["size"]
         st = _lib.current_stream()
-        img = image if torch.is_tensor(image) else torch.from_numpy(np.ascontiguousarray(image))
-        assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3, img.shape
-        img = img.to(self.device, non_blocking=True).contiguous()
         H, W = int(img.shape[0]), int(img.shape[1])
         (x0, y0, cw, ch), (rh, rw), (ox, oy), flip = p["crop1"], p["resize"], p["crop2"], int(p["flip"])
         vh, vw = min(rh - oy, S), min(rw - ox, S)
@@ -164,26 +245,106 @@ class DeviceProposalMapper:
         ratio = a[nonempty] / a[nonempty].sum()
         return nonempty[ratio > self.min_area_ratio]
 
-    def __call__(self, dataset_dict):
-        """dataset_dict: {"image": decoded uint8 HWC array (or "file_name" readable by Pillow), "pseudo_annotations":
-        [{"segmentation": COCO RLE dict, "category_id"?}], ...} -> the reference mapper's output dict, tensors on the device"""
+    @staticmethod
+    def _read_image(dataset_dict):
         image = dataset_dict.get("image")
         if image is None:
             from PIL import Image
             image = np.asarray(Image.open(dataset_dict["file_name"]).convert("RGB"))
+        return image
+
+    def _output(self, dataset_dict, image, padding, masks, classes, size):
+        inst = Instances(size)
+        inst.gt_masks = BitMasks(masks)
+        inst.gt_classes = classes
+        out = {k: v for k, v in dataset_dict.items() if k not in ("pseudo_annotations", "image")}
+        out.update(image=image, padding_mask=padding, instances=inst, height=size[0], width=size[1])
+        return out
+
+    def __call__(self, dataset_dict):
+        """dataset_dict: {"image": decoded uint8 HWC array (or "file_name" readable by Pillow), "pseudo_annotations":
+        [{"segmentation": COCO RLE dict, "category_id"?}], ...}, or the (dataset_path, class_code, file) tuple of a PATH_ONLY dataset
+        -> the reference mapper's output dict, tensors on the device (None when load_annotation drops the image).  With the base
+        stage on, the masks' RLE size is the base canvas, not the decoded image (`transform` asserts it)."""
+        if isinstance(dataset_dict, tuple):
+            dataset_dict = self.load_annotation(dataset_dict)
+            if dataset_dict is None:
+                return None
+        image = self._read_image(dataset_dict)
+        if self.base_size > 0:
+            image = self.base_image(image)                                   # once: it does not depend on the draws
         annos = dataset_dict["pseudo_annotations"]
         segs = [a["segmentation"] for a in annos]
-        classes = torch.tensor([a.get("category_id", -1) for a in annos], dtype=torch.int64)
+        classes = torch.tensor([int(a.get("category_id", -1)) for a in annos], dtype=torch.int64)
         H, W = int(image.shape[0]), int(image.shape[1])
-        for attempt in range(self.num_repeats + 1):
+        repeats = self._repeats(annos)
+        for attempt in range(repeats + 1):
             p = self.draw(H, W, weak=attempt == self.num_repeats)            # last resort: the weak augmentation (:160-164)
             img, masks, padding, area = self.transform(image, segs, p)
             keep = self.select(masks, area)
-            if keep.numel() > 0 or attempt == self.num_repeats:
+            if keep.numel() > 0 or attempt == repeats:
                 break
-        inst = Instances((self.image_size, self.image_size))
-        inst.gt_masks = BitMasks(masks[keep])
-        inst.gt_classes = classes.to(self.device)[keep]
-        out = {k: v for k, v in dataset_dict.items() if k not in ("pseudo_annotations", "image")}
-        out.update(image=img, padding_mask=padding, instances=inst, height=self.image_size, width=self.image_size)
-        return out
+        return self._output(dataset_dict, img, padding, masks[keep], classes.to(self.device)[keep], (self.image_size, self.image_size))
+
+    def _repeats(self, annos):
+        return self.num_repeats
+
+
+class DevicePartDistillationMapper(DeviceProposalMapper):
+    """the reference's PartDistillationDatasetMapper, which part_distillation_train_net.py builds for its train AND its test loader:
+    the base stage always on, part labels as gt_classes, a score filter on the saved parts, and `is_train=False` = the reference's
+    `test_aug = []` — the base canvas itself with the decoded masks, no augmentation and no draws."""
+
+    def __init__(self, *args, is_train=True, min_score=-1.0, **kw):
+        super().__init__(*args, **kw)
+        if self.base_size <= 0:
+            raise ValueError("DevicePartDistillationMapper: base_size (CUSTOM_DATASETS.BASE_SIZE) must be positive, the reference's "
+                             "mapper always resizes to it")
+        self.is_train, self.min_score = bool(is_train), min_score
+
+    @classmethod
+    def from_config(cls, cfg, is_train=True, device=None, class_code_to_class_id=None):
+        """reference part_distillation_dataset_mapper.py:52-126"""
+        pd = cfg.PART_DISTILLATION
+        return cls(*cls._augmentation_args(cfg), pd.MIN_AREA_RATIO, pd.MIN_OBJECT_AREA_RATIO, device or cfg.MODEL.DEVICE,
+                   base_size=cfg.CUSTOM_DATASETS.BASE_SIZE, square_base=pd.SET_IMAGE_SQUARE, class_code_to_class_id=class_code_to_class_id,
+                   is_train=is_train, min_score=pd.MIN_SCORE)
+
+    def load_annotation(self, path_tuple):
+        """reference :130-164: the dict save_generated_part_labels / save_part_segmentation write (part_labels a tensor, part_scores a
+        numpy array, part_ratios a tensor or absent) -> dataset dict with the parts that pass the ratio and score filters, or None"""
+        ann = self._load_saved(path_tuple)
+        if ann is None or not ann["object_ratio"] >= self.min_object_area_ratio or not ann["part_masks"]:
+            return None
+        parts = []
+        for i, (lbl, m) in enumerate(zip(ann["part_labels"], ann["part_masks"])):
+            if "part_ratios" in ann and not ann["part_ratios"][i] >= self.min_area_ratio:
+                continue
+            if "part_scores" in ann and not ann["part_scores"][i] >= self.min_score:
+                continue
+            parts.append({"segmentation": m["segmentation"], "category_id": int(lbl)})
+        if not parts:
+            return None
+        h, w = parts[-1]["segmentation"]["size"]
+        return {"file_name": ann["file_name"], "image_id": ann["image_id"], "class_code": path_tuple[1], "height": h, "width": w,
+                "pseudo_annotations": parts, "gt_object_class": self.class_code_to_class_id[ann["class_code"]]}
+
+    def _repeats(self, annos):
+        return self.num_repeats if len(annos) else 0                         # nothing to retry for: one pass, zero-length instances
+
+    def __call__(self, dataset_dict):
+        if self.is_train:
+            return super().__call__(dataset_dict)
+        if isinstance(dataset_dict, tuple):
+            dataset_dict = self.load_annotation(dataset_dict)
+            if dataset_dict is None:
+                return None
+        from ..functions import rle as device_rle
+        image = self.base_image(self._read_image(dataset_dict), planar=True)
+        size = (int(image.shape[1]), int(image.shape[2]))
+        annos = dataset_dict["pseudo_annotations"]
+        classes = torch.tensor([int(a.get("category_id", -1)) for a in annos], dtype=torch.int64, device=self.device)
+        masks = device_rle.decode_masks([a["segmentation"] for a in annos], size, self.device)
+        keep = self.select(masks, masks.flatten(1).sum(1, dtype=torch.int32))
+        padding = torch.zeros(size, dtype=torch.bool, device=self.device)
+        return self._output(dataset_dict, image, padding, masks[keep], classes[keep], size)
