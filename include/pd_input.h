@@ -24,6 +24,24 @@
  *   pd_rle_sample_u8      all masks of the image, straight from their run lengths (no dense full-resolution mask):
  *                         out[i][y][x] = inside ? parity(search(starts_i, colmajor(src_x[x], src_y[y]))) : 0, and
  *                         area[i] += popcount — src_x / src_y = the composed nearest-neighbour index tables
+ *   pd_rle_sample_groups_u8   the ground-truth mappers' sampling (reference voc_parts_mapper.py / cityscapes_part_mapper.py: decode, Pillow
+ *                         NEAREST resize, flip, crop, then the per-object, per-class merge): n member masks, n_groups RECTANGULAR output
+ *                         planes given as a CSR list of member indices (group g = group_members[group_offsets[g] .. group_offsets[g + 1])),
+ *                         out[g][y][x] = OR over the members m of g of parity(search(starts_m, src_x[x] * H + src_y[y]))   (0 / 1),
+ *                         member_area[m] = set output pixels of member m on its own (also of a member that is in no group),
+ *                         group_area[g]  = set pixels of plane g (the union is counted once).
+ *                         src_x[out_w] / src_y[out_h] are source columns / rows in any order, with repeats and gaps: the host composes
+ *                         resize, flip and crop into them, so there is no flip argument and no inside window.  A member may be in none,
+ *                         one or several groups, a group may be empty (plane and area 0).  out is [n_groups, out_h, out_w] contiguous.
+ *                         EVERY byte of out, member_area and group_area is written by the call (the counts are zeroed by the entry point;
+ *                         the caller pre-zeroes nothing); the counts are integer sums, so the result is bit-reproducible.
+ *                         PD_ERR_INVALID_ARG before any launch: a negative n or n_groups, n_groups > PD_SAMPLE_GROUPS_MAX, H or W < 1,
+ *                         H * W > 2^31 - 1, out_h or out_w outside 1..PD_CANVAS_MAX_SIDE, a null pointer that would be read or written
+ *                         (group_members may be null when n == 0 or n_groups == 0: it is not read then).  n_groups == 0 still fills
+ *                         member_area; n == 0 fills the planes and group_area with zeros; n == 0 && n_groups == 0 returns PD_OK without
+ *                         a launch.  The launch is a flat grid-stride one, so no grid dimension grows with n, n_groups or the canvas;
+ *                         PD_SAMPLE_GROUPS_MAX only bounds the plane count an image can ask for.  group_members come from the host:
+ *                         the caller checks their range (the kernel skips an index outside [0, n) rather than read through it).
  *
  * src: uint8 [H, W, 3] (HWC, as decoded).  Tables int32.  kk: Pillow's 22-bit fixed-point coefficients [n, ksize].
  * starts: int32, for mask i the entries [offsets[i], offsets[i+1]) are the EXCLUSIVE prefix sums of its COCO run lengths
@@ -51,6 +69,11 @@ int pd_resample_cols_canvas_u8(const uint8_t *tmp, int tmp_rows, int tmp_w, int 
 
 int pd_rle_sample_u8(const int32_t *starts, const int32_t *offsets, int n_masks, int H, int W, int flip, const int32_t *src_x,
                      const int32_t *src_y, int vh, int vw, int S, uint8_t *out, int32_t *area, void *stream);
+
+#define PD_SAMPLE_GROUPS_MAX (1 << 20)
+int pd_rle_sample_groups_u8(const int32_t *starts, const int32_t *offsets, int n, int H, int W, const int32_t *src_x, const int32_t *src_y,
+                            int out_h, int out_w, const int32_t *group_offsets, const int32_t *group_members, int n_groups, uint8_t *out,
+                            int32_t *member_area, int32_t *group_area, void *stream);
 
 /*
  * out [B, H, W, 3] fp32 (the channels-last storage of the [B, 3, H, W] batch) = (images[b] - mean) / std for B same-size planar uint8

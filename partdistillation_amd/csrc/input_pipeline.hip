@@ -99,6 +99,75 @@ __global__ __launch_bounds__(256) void rle_sample(const int32_t *__restrict__ st
   const unsigned long long ball = __ballot(v != 0);
   if ((threadIdx.x & 63) == 0 && ball) atomicAdd(area + i, __popcll(ball));
 }
+// pd_rle_sample_groups_u8: one work unit per output plane (the OR of a group's members) and one per member (its own pixel count), cut into
+// tiles of SG_TILE consecutive pixels of the flat out_h x out_w plane, so every store is 64 consecutive bytes per wave whatever the pitch.
+// A thread keeps the column-major positions of its SG_PIX pixels in registers; the members of the unit pass through LDS one after the
+// other (a run table is a few hundred bytes and is searched 2048 times per tile), tables longer than SG_LDS_RUNS are searched in place.
+constexpr int SG_PIX = 8, SG_TILE = 256 * SG_PIX, SG_LDS_RUNS = 2048, SG_MAX_BLOCKS = 4096;
+
+__global__ __launch_bounds__(256) void rle_sample_groups(const int32_t *__restrict__ starts, const int32_t *__restrict__ offsets, int n, int H,
+                                                         const int32_t *__restrict__ src_x, const int32_t *__restrict__ src_y, uint32_t out_w,
+                                                         uint32_t plane, const int32_t *__restrict__ group_offsets,
+                                                         const int32_t *__restrict__ group_members, int n_groups, uint8_t *__restrict__ out,
+                                                         int32_t *__restrict__ member_area, int32_t *__restrict__ group_area,
+                                                         uint32_t tiles_per_plane, int64_t total_tiles)
+{
+  __shared__ int32_t runs[SG_LDS_RUNS];
+  __shared__ int tile_count;
+  const int tid = threadIdx.x;
+  for (int64_t t = blockIdx.x; t < total_tiles; t += gridDim.x) {
+    const int unit = (int)(t / tiles_per_plane);
+    const uint32_t p0 = (uint32_t)(t - (int64_t)unit * tiles_per_plane) * SG_TILE + tid;
+    int pos[SG_PIX];
+#pragma unroll
+    for (int k = 0; k < SG_PIX; ++k) {
+      const uint32_t p = p0 + k * 256;
+      pos[k] = -1;                                                        // past the plane: before every run start, value 0
+      if (p < plane) {
+        const uint32_t y = p / out_w, x = p - y * out_w;
+        pos[k] = src_x[x] * H + src_y[y];
+      }
+    }
+    const bool is_group = unit < n_groups;
+    int mb = unit - n_groups, me = mb + 1;                                // a member on its own
+    if (is_group) { mb = group_offsets[unit]; me = n > 0 ? group_offsets[unit + 1] : mb; }
+    if (tid == 0) tile_count = 0;
+    unsigned bits = 0;
+    for (int j = mb; j < me; ++j) {                                       // block-uniform: the barriers below are reached by all
+      const int m = is_group ? group_members[j] : j;
+      if ((unsigned)m >= (unsigned)n) continue;
+      const int a = offsets[m], cnt = offsets[m + 1] - a;
+      if (cnt <= SG_LDS_RUNS) {
+        __syncthreads();                                                  // the searches of the member before
+        for (int i = tid; i < cnt; i += 256) runs[i] = starts[a + i];
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < SG_PIX; ++k)
+          if (!((bits >> k) & 1)) bits |= (unsigned)(pd_rle_find_run(runs, cnt, pos[k]) & 1) << k;
+      } else {
+#pragma unroll
+        for (int k = 0; k < SG_PIX; ++k)
+          if (!((bits >> k) & 1)) bits |= (unsigned)(pd_rle_find_run(starts + a, cnt, pos[k]) & 1) << k;
+      }
+    }
+    if (is_group) {
+      uint8_t *o = out + (int64_t)unit * plane;
+#pragma unroll
+      for (int k = 0; k < SG_PIX; ++k) {
+        const uint32_t p = p0 + k * 256;
+        if (p < plane) o[p] = (uint8_t)((bits >> k) & 1);
+      }
+    }
+    // counts: wave, then block through LDS, then one global atomic per tile, zeros skipped
+    int c = __popc(bits);
+#pragma unroll
+    for (int off = 32; off; off >>= 1) c += __shfl_xor(c, off);
+    __syncthreads();                                                      // tile_count = 0 is visible
+    if ((tid & 63) == 0 && c) atomicAdd(&tile_count, c);
+    __syncthreads();
+    if (tid == 0 && tile_count) atomicAdd(is_group ? group_area + unit : member_area + (unit - n_groups), tile_count);
+  }
+}
 }  // namespace
 
 extern "C" int pd_resample_rows_u8(const uint8_t *src, int H, int W, int row0, int rows, int x0, int flip, const int32_t *xmin,
@@ -154,6 +223,33 @@ extern "C" int pd_rle_sample_u8(const int32_t *starts, const int32_t *offsets, i
   hipLaunchKernelGGL(rle_sample, dim3((S + 255) / 256, S, n_masks), dim3(256), 0, (hipStream_t)stream_, starts, offsets, H, W, flip, src_x,
                      src_y, vh, vw, S, out, area);
   return pd_check_launch("pd_rle_sample_u8");
+}
+
+extern "C" int pd_rle_sample_groups_u8(const int32_t *starts, const int32_t *offsets, int n, int H, int W, const int32_t *src_x,
+                                       const int32_t *src_y, int out_h, int out_w, const int32_t *group_offsets, const int32_t *group_members,
+                                       int n_groups, uint8_t *out, int32_t *member_area, int32_t *group_area, void *stream_)
+{
+  if (n < 0 || n_groups < 0 || n_groups > PD_SAMPLE_GROUPS_MAX || H <= 0 || W <= 0 || (int64_t)H * W > 0x7fffffffLL || out_h <= 0 || out_w <= 0 ||
+      out_h > PD_CANVAS_MAX_SIDE || out_w > PD_CANVAS_MAX_SIDE)
+    return pd_set_error(PD_ERR_INVALID_ARG, "pd_rle_sample_groups_u8: bad sizes n=%d n_groups=%d (<= %d) H=%d W=%d out=%dx%d (sides 1..%d)", n,
+                        n_groups, PD_SAMPLE_GROUPS_MAX, H, W, out_h, out_w, PD_CANVAS_MAX_SIDE);
+  if (n == 0 && n_groups == 0) return PD_OK;
+  if (!src_x || !src_y || (n > 0 && (!starts || !offsets || !member_area)) || (n_groups > 0 && (!group_offsets || !out || !group_area)) ||
+      (n > 0 && n_groups > 0 && !group_members))
+    return pd_set_error(PD_ERR_INVALID_ARG, "pd_rle_sample_groups_u8: null pointer");
+  hipStream_t stream = (hipStream_t)stream_;
+  // the counts are atomic sums: zero them here, the caller pre-zeroes nothing (the planes are written whole by the kernel)
+  if (n > 0 && hipMemsetAsync(member_area, 0, (size_t)n * sizeof(int32_t), stream) != hipSuccess) return pd_check_launch("pd_rle_sample_groups_u8 (memset)");
+  if (n_groups > 0 && hipMemsetAsync(group_area, 0, (size_t)n_groups * sizeof(int32_t), stream) != hipSuccess)
+    return pd_check_launch("pd_rle_sample_groups_u8 (memset)");
+  const uint32_t plane = (uint32_t)out_h * (uint32_t)out_w;               // <= 65535^2 < 2^32
+  const uint32_t tiles_per_plane = (plane + SG_TILE - 1) / SG_TILE;
+  const int64_t total = ((int64_t)n_groups + n) * tiles_per_plane;
+  // a flat grid-stride launch: no grid dimension grows with the planes, the members or the canvas
+  const unsigned grid = (unsigned)(total < SG_MAX_BLOCKS ? total : SG_MAX_BLOCKS);
+  hipLaunchKernelGGL(rle_sample_groups, dim3(grid), dim3(256), 0, stream, starts, offsets, n, H, src_x, src_y, (uint32_t)out_w, plane,
+                     group_offsets, group_members, n_groups, out, member_area, group_area, tiles_per_plane, total);
+  return pd_check_launch("pd_rle_sample_groups_u8");
 }
 
 // (x - mean) / std of B same-size planar uint8 images [3, H, W] written straight into the channels-last fp32 batch the backbone reads

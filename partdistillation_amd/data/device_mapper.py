@@ -66,6 +66,24 @@ def nearest_index(in_size, out_size):
     return np.clip(np.cumsum(steps).astype(np.int64), 0, in_size - 1).astype(np.int32)
 
 
+def random_crop(rng, h, w, crop_type, crop_size):
+    """detectron2 0.6 RandomCrop.get_transform of an h x w image: get_crop_size's draws, then the row and the column offset
+    -> (x0, y0, cw, ch)"""
+    if crop_type == "relative":
+        ch, cw = int(h * crop_size[0] + 0.5), int(w * crop_size[1] + 0.5)
+    elif crop_type == "relative_range":
+        cs = np.asarray(crop_size, dtype=np.float32)
+        chf, cwf = cs + rng.rand(2) * (1 - cs)
+        ch, cw = int(h * chf + 0.5), int(w * cwf + 0.5)
+    elif crop_type == "absolute":
+        ch, cw = min(crop_size[0], h), min(crop_size[1], w)
+    else:
+        raise NotImplementedError(crop_type)
+    y0 = rng.randint(h - ch + 1)
+    x0 = rng.randint(w - cw + 1)
+    return int(x0), int(y0), int(cw), int(ch)
+
+
 class DeviceProposalMapper:
     def __init__(self, image_size, min_scale=0.1, max_scale=2.0, crop_type=None, crop_size=None, flip=True, min_area_ratio=0.0,
                  min_object_area_ratio=0.0, device="cuda", rng=None, pad_value=128, num_repeats=100, base_size=-1, square_base=False,
@@ -140,20 +158,8 @@ class DeviceProposalMapper:
         h, w = in_h, in_w
         p["crop1"] = (0, 0, w, h)
         if self.crop_type is not None and not weak:
-            if self.crop_type == "relative":
-                ch, cw = int(h * self.crop_size[0] + 0.5), int(w * self.crop_size[1] + 0.5)
-            elif self.crop_type == "relative_range":
-                cs = np.asarray(self.crop_size, dtype=np.float32)
-                chf, cwf = cs + rng.rand(2) * (1 - cs)
-                ch, cw = int(h * chf + 0.5), int(w * cwf + 0.5)
-            elif self.crop_type == "absolute":
-                ch, cw = min(self.crop_size[0], h), min(self.crop_size[1], w)
-            else:
-                raise NotImplementedError(self.crop_type)
-            y0 = rng.randint(h - ch + 1)
-            x0 = rng.randint(w - cw + 1)
-            p["crop1"] = (int(x0), int(y0), int(cw), int(ch))
-            h, w = ch, cw
+            p["crop1"] = random_crop(rng, h, w, self.crop_type, self.crop_size)
+            h, w = p["crop1"][3], p["crop1"][2]
         s = rng.uniform(1.0, 1.0) if weak else rng.uniform(self.min_scale, self.max_scale)
         out_scale = min(S * s / h, S * s / w)
         rh, rw = int(np.round(h * out_scale)), int(np.round(w * out_scale))
