@@ -32,6 +32,7 @@
 #include "pd_msda.h"
 #include "pd_mx8.h"
 #include "pd_optim.h"
+#include "pd_poly.h"
 #include "pd_rowwise.h"
 #include "pd_smallgemm.h"
 #include "pd_stem.h"
@@ -171,6 +172,7 @@ const Entry kTable[] = {
   PD_E(pd_point_sample_planar_bwd_f32),
   PD_E(pd_point_sample_planar_f32),
   PD_E(pd_point_sample_u8),
+  PD_E(pd_poly_crossings_i32),
   PD_E(pd_relu_bwd_colsum),
   PD_E(pd_resample_cols_canvas_u8),
   PD_E(pd_resample_cols_u8),

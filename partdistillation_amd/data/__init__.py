@@ -1,2 +1,3 @@
 from .device_mapper import DevicePartDistillationMapper, DeviceProposalMapper  # noqa: F401
 from .gt_part_mapper import DeviceCityscapesPartMapper, DeviceGTPartMapper, DeviceVOCPartsMapper  # noqa: F401
+from .part_imagenet_mapper import DevicePartImageNetMapper  # noqa: F401

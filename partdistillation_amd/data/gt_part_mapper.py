@@ -83,9 +83,12 @@ def group_table(n_obj, part_obj, part_cls, part_ok, merged):
     return offsets, members, np.asarray(g_obj, dtype=np.int64), np.asarray(g_cls, dtype=np.int64)
 
 
-def rle_sample_groups(starts, offsets, H, W, src_x, src_y, group_offsets, group_members, out=None, member_area=None, group_area=None):
+def rle_sample_groups(starts, offsets, H, W, src_x, src_y, group_offsets, group_members, out=None, member_area=None, group_area=None,
+                      uploaded=None):
     """pd_rle_sample_groups_u8 on device tensors (int32 tables; the group table may be host numpy: its member indices are range-checked
-    here, before upload) -> (planes uint8 [G, out_h, out_w], member_area int32 [n], group_area int32 [G]); nothing is pre-zeroed"""
+    here, before upload) -> (planes uint8 [G, out_h, out_w], member_area int32 [n], group_area int32 [G]); nothing is pre-zeroed.
+    `uploaded`: device int32 copies (group_offsets, group_members padded by one entry) of the host group table the caller has already
+    sent with another upload; the host table is still what is checked"""
     dev = src_x.device
     n, G = int(offsets.numel()) - 1, len(group_offsets) - 1
     go, gm = (np.asarray(a.cpu() if torch.is_tensor(a) else a, dtype=np.int64).reshape(-1) for a in (group_offsets, group_members))
@@ -93,8 +96,12 @@ def rle_sample_groups(starts, offsets, H, W, src_x, src_y, group_offsets, group_
         raise ValueError("rle_sample_groups: group_offsets is not a CSR offset vector of group_members")
     if len(gm) and (gm.min() < 0 or gm.max() >= n):
         raise ValueError(f"rle_sample_groups: member index outside [0, {n})")
-    d_go = torch.from_numpy(go.astype(np.int32)).to(dev, non_blocking=True)
-    d_gm = torch.from_numpy(np.concatenate((gm, [0])).astype(np.int32)).to(dev, non_blocking=True)      # never a null pointer
+    if uploaded is not None:
+        d_go, d_gm = uploaded
+        assert d_go.dtype == torch.int32 and d_gm.dtype == torch.int32 and d_go.numel() == len(go) and d_gm.numel() > len(gm)
+    else:
+        d_go = torch.from_numpy(go.astype(np.int32)).to(dev, non_blocking=True)
+        d_gm = torch.from_numpy(np.concatenate((gm, [0])).astype(np.int32)).to(dev, non_blocking=True)  # never a null pointer
     out_h, out_w = int(src_y.numel()), int(src_x.numel())
     out = torch.empty((G, out_h, out_w), dtype=torch.uint8, device=dev) if out is None else out
     member_area = torch.empty(n, dtype=torch.int32, device=dev) if member_area is None else member_area
@@ -117,8 +124,8 @@ class DeviceGTPartMapper:
     def __init__(self, is_train, min_size, max_size, sample_style="choice", crop_type=None, crop_size=None, use_merged_gt=True,
                  device="cuda", rng=None, mask_format="bitmask"):
         if mask_format != "bitmask":
-            raise NotImplementedError(f"INPUT.MASK_FORMAT '{mask_format}': polygon ground truth (the PartImageNet route) goes through "
-                                      "pycocotools' rasteriser, which is not restated here; only RLE segmentations are mapped")
+            raise NotImplementedError(f"INPUT.MASK_FORMAT '{mask_format}': polygon ground truth is DevicePartImageNetMapper's "
+                                      "(part_imagenet_mapper.py); this mapper maps RLE segmentations only")
         self.is_train = bool(is_train)
         self.min_size = tuple(int(s) for s in (min_size if isinstance(min_size, (tuple, list)) else (min_size, min_size)))
         self.max_size, self.sample_style = int(max_size), sample_style
@@ -216,8 +223,8 @@ class DeviceGTPartMapper:
         segs = [o["segmentation"] for _, o in objs] + [part["segmentation"] for _, part in parts]
         for s in segs:
             if not isinstance(s, dict):
-                raise NotImplementedError("polygon segmentations (PartImageNetMapper, INPUT.MASK_FORMAT 'polygon') are not mapped: "
-                                          "pycocotools' rasteriser is not restated here; encode the masks as COCO RLE")
+                raise NotImplementedError("polygon segmentations (INPUT.MASK_FORMAT 'polygon') are not mapped by this mapper: they are "
+                                          "DevicePartImageNetMapper's (part_imagenet_mapper.py); encode the masks as COCO RLE")
         rec = {"obj_index": np.asarray([i for i, _ in objs], dtype=np.int64),
                "obj_cls": np.asarray([int(o["category_id"]) for _, o in objs], dtype=np.int64),
                "obj_box": np.asarray([self._xyxy(o) for _, o in objs], dtype=np.float64).reshape(-1, 4),
