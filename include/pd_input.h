@@ -42,6 +42,14 @@
  *                         a launch.  The launch is a flat grid-stride one, so no grid dimension grows with n, n_groups or the canvas;
  *                         PD_SAMPLE_GROUPS_MAX only bounds the plane count an image can ask for.  group_members come from the host:
  *                         the caller checks their range (the kernel skips an index outside [0, n) rather than read through it).
+ *   pd_rle_sample_groups_canvas_u8   the same sampling onto a PADDED canvas (reference imagenet_part_ranking_dataset_mapper.py: FixedSizeCrop's
+ *                         zero pad of the masks, then `gt_masks.tensor.sum(0)[None]`): the contract above with a valid window of vh x vw in the
+ *                         top-left corner of each out_h x out_w plane.  src_x has vw entries and src_y has vh;
+ *                         out[g][y][x] for y < vh && x < vw is the OR over the group's members as above, every other byte of the plane is 0
+ *                         and counts in neither area.  vh == 0 or vw == 0 still writes all-zero planes and zero counts.  The argument
+ *                         checks are those above, plus: vh or vw negative, vh > out_h or vw > out_w are PD_ERR_INVALID_ARG (before the
+ *                         memsets and the launch); src_x / src_y may be null only when the window is empty.  pd_rle_sample_groups_u8 is
+ *                         this entry with vh = out_h, vw = out_w: one kernel serves both.
  *
  * src: uint8 [H, W, 3] (HWC, as decoded).  Tables int32.  kk: Pillow's 22-bit fixed-point coefficients [n, ksize].
  * starts: int32, for mask i the entries [offsets[i], offsets[i+1]) are the EXCLUSIVE prefix sums of its COCO run lengths
@@ -74,6 +82,10 @@ int pd_rle_sample_u8(const int32_t *starts, const int32_t *offsets, int n_masks,
 int pd_rle_sample_groups_u8(const int32_t *starts, const int32_t *offsets, int n, int H, int W, const int32_t *src_x, const int32_t *src_y,
                             int out_h, int out_w, const int32_t *group_offsets, const int32_t *group_members, int n_groups, uint8_t *out,
                             int32_t *member_area, int32_t *group_area, void *stream);
+
+int pd_rle_sample_groups_canvas_u8(const int32_t *starts, const int32_t *offsets, int n, int H, int W, const int32_t *src_x, const int32_t *src_y,
+                                   int vh, int vw, int out_h, int out_w, const int32_t *group_offsets, const int32_t *group_members,
+                                   int n_groups, uint8_t *out, int32_t *member_area, int32_t *group_area, void *stream);
 
 /*
  * out [B, H, W, 3] fp32 (the channels-last storage of the [B, 3, H, W] batch) = (images[b] - mean) / std for B same-size planar uint8

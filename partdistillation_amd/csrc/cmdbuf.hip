@@ -178,6 +178,7 @@ const Entry kTable[] = {
   PD_E(pd_resample_cols_u8),
   PD_E(pd_resample_rows_u8),
   PD_E(pd_resize_bilinear_nhwc_f32),
+  PD_E(pd_rle_sample_groups_canvas_u8),
   PD_E(pd_rle_sample_groups_u8),
   PD_E(pd_rle_sample_u8),
   PD_E(pd_row_amax_f32),

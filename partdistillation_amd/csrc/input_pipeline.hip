@@ -99,15 +99,18 @@ __global__ __launch_bounds__(256) void rle_sample(const int32_t *__restrict__ st
   const unsigned long long ball = __ballot(v != 0);
   if ((threadIdx.x & 63) == 0 && ball) atomicAdd(area + i, __popcll(ball));
 }
-// pd_rle_sample_groups_u8: one work unit per output plane (the OR of a group's members) and one per member (its own pixel count), cut into
-// tiles of SG_TILE consecutive pixels of the flat out_h x out_w plane, so every store is 64 consecutive bytes per wave whatever the pitch.
+// pd_rle_sample_groups_u8 / pd_rle_sample_groups_canvas_u8: one work unit per output plane (the OR of a group's members) and one per member
+// (its own pixel count), cut into tiles of SG_TILE consecutive pixels of the flat out_h x out_w plane, so every store is 64 consecutive
+// bytes per wave whatever the pitch.
 // A thread keeps the column-major positions of its SG_PIX pixels in registers; the members of the unit pass through LDS one after the
 // other (a run table is a few hundred bytes and is searched 2048 times per tile), tables longer than SG_LDS_RUNS are searched in place.
+// Only the vh x vw window in the top-left corner of a plane is sampled (the whole plane for pd_rle_sample_groups_u8): a pixel outside it
+// reads no table and is a 0 that counts in no area.
 constexpr int SG_PIX = 8, SG_TILE = 256 * SG_PIX, SG_LDS_RUNS = 2048, SG_MAX_BLOCKS = 4096;
 
 __global__ __launch_bounds__(256) void rle_sample_groups(const int32_t *__restrict__ starts, const int32_t *__restrict__ offsets, int n, int H,
-                                                         const int32_t *__restrict__ src_x, const int32_t *__restrict__ src_y, uint32_t out_w,
-                                                         uint32_t plane, const int32_t *__restrict__ group_offsets,
+                                                         const int32_t *__restrict__ src_x, const int32_t *__restrict__ src_y, uint32_t vh,
+                                                         uint32_t vw, uint32_t out_w, uint32_t plane, const int32_t *__restrict__ group_offsets,
                                                          const int32_t *__restrict__ group_members, int n_groups, uint8_t *__restrict__ out,
                                                          int32_t *__restrict__ member_area, int32_t *__restrict__ group_area,
                                                          uint32_t tiles_per_plane, int64_t total_tiles)
@@ -122,10 +125,10 @@ __global__ __launch_bounds__(256) void rle_sample_groups(const int32_t *__restri
 #pragma unroll
     for (int k = 0; k < SG_PIX; ++k) {
       const uint32_t p = p0 + k * 256;
-      pos[k] = -1;                                                        // past the plane: before every run start, value 0
+      pos[k] = -1;                                                        // past the plane or the window: before every run start, value 0
       if (p < plane) {
         const uint32_t y = p / out_w, x = p - y * out_w;
-        pos[k] = src_x[x] * H + src_y[y];
+        if (y < vh && x < vw) pos[k] = src_x[x] * H + src_y[y];
       }
     }
     const bool is_group = unit < n_groups;
@@ -225,6 +228,26 @@ extern "C" int pd_rle_sample_u8(const int32_t *starts, const int32_t *offsets, i
   return pd_check_launch("pd_rle_sample_u8");
 }
 
+namespace {
+// the shared tail of the two sampling entry points, after their argument checks
+int launch_sample_groups(const char *who, const int32_t *starts, const int32_t *offsets, int n, int H, const int32_t *src_x, const int32_t *src_y,
+                         int vh, int vw, int out_h, int out_w, const int32_t *group_offsets, const int32_t *group_members, int n_groups,
+                         uint8_t *out, int32_t *member_area, int32_t *group_area, hipStream_t stream)
+{
+  // the counts are atomic sums: zero them here, the caller pre-zeroes nothing (the planes are written whole by the kernel)
+  if (n > 0 && hipMemsetAsync(member_area, 0, (size_t)n * sizeof(int32_t), stream) != hipSuccess) return pd_check_launch(who);
+  if (n_groups > 0 && hipMemsetAsync(group_area, 0, (size_t)n_groups * sizeof(int32_t), stream) != hipSuccess) return pd_check_launch(who);
+  const uint32_t plane = (uint32_t)out_h * (uint32_t)out_w;               // <= 65535^2 < 2^32
+  const uint32_t tiles_per_plane = (plane + SG_TILE - 1) / SG_TILE;
+  const int64_t total = ((int64_t)n_groups + n) * tiles_per_plane;
+  // a flat grid-stride launch: no grid dimension grows with the planes, the members or the canvas
+  const unsigned grid = (unsigned)(total < SG_MAX_BLOCKS ? total : SG_MAX_BLOCKS);
+  hipLaunchKernelGGL(rle_sample_groups, dim3(grid), dim3(256), 0, stream, starts, offsets, n, H, src_x, src_y, (uint32_t)vh, (uint32_t)vw,
+                     (uint32_t)out_w, plane, group_offsets, group_members, n_groups, out, member_area, group_area, tiles_per_plane, total);
+  return pd_check_launch(who);
+}
+}  // namespace
+
 extern "C" int pd_rle_sample_groups_u8(const int32_t *starts, const int32_t *offsets, int n, int H, int W, const int32_t *src_x,
                                        const int32_t *src_y, int out_h, int out_w, const int32_t *group_offsets, const int32_t *group_members,
                                        int n_groups, uint8_t *out, int32_t *member_area, int32_t *group_area, void *stream_)
@@ -237,19 +260,26 @@ extern "C" int pd_rle_sample_groups_u8(const int32_t *starts, const int32_t *off
   if (!src_x || !src_y || (n > 0 && (!starts || !offsets || !member_area)) || (n_groups > 0 && (!group_offsets || !out || !group_area)) ||
       (n > 0 && n_groups > 0 && !group_members))
     return pd_set_error(PD_ERR_INVALID_ARG, "pd_rle_sample_groups_u8: null pointer");
-  hipStream_t stream = (hipStream_t)stream_;
-  // the counts are atomic sums: zero them here, the caller pre-zeroes nothing (the planes are written whole by the kernel)
-  if (n > 0 && hipMemsetAsync(member_area, 0, (size_t)n * sizeof(int32_t), stream) != hipSuccess) return pd_check_launch("pd_rle_sample_groups_u8 (memset)");
-  if (n_groups > 0 && hipMemsetAsync(group_area, 0, (size_t)n_groups * sizeof(int32_t), stream) != hipSuccess)
-    return pd_check_launch("pd_rle_sample_groups_u8 (memset)");
-  const uint32_t plane = (uint32_t)out_h * (uint32_t)out_w;               // <= 65535^2 < 2^32
-  const uint32_t tiles_per_plane = (plane + SG_TILE - 1) / SG_TILE;
-  const int64_t total = ((int64_t)n_groups + n) * tiles_per_plane;
-  // a flat grid-stride launch: no grid dimension grows with the planes, the members or the canvas
-  const unsigned grid = (unsigned)(total < SG_MAX_BLOCKS ? total : SG_MAX_BLOCKS);
-  hipLaunchKernelGGL(rle_sample_groups, dim3(grid), dim3(256), 0, stream, starts, offsets, n, H, src_x, src_y, (uint32_t)out_w, plane,
-                     group_offsets, group_members, n_groups, out, member_area, group_area, tiles_per_plane, total);
-  return pd_check_launch("pd_rle_sample_groups_u8");
+  return launch_sample_groups("pd_rle_sample_groups_u8", starts, offsets, n, H, src_x, src_y, out_h, out_w, out_h, out_w, group_offsets,
+                              group_members, n_groups, out, member_area, group_area, (hipStream_t)stream_);
+}
+
+extern "C" int pd_rle_sample_groups_canvas_u8(const int32_t *starts, const int32_t *offsets, int n, int H, int W, const int32_t *src_x,
+                                              const int32_t *src_y, int vh, int vw, int out_h, int out_w, const int32_t *group_offsets,
+                                              const int32_t *group_members, int n_groups, uint8_t *out, int32_t *member_area,
+                                              int32_t *group_area, void *stream_)
+{
+  if (n < 0 || n_groups < 0 || n_groups > PD_SAMPLE_GROUPS_MAX || H <= 0 || W <= 0 || (int64_t)H * W > 0x7fffffffLL || out_h <= 0 || out_w <= 0 ||
+      out_h > PD_CANVAS_MAX_SIDE || out_w > PD_CANVAS_MAX_SIDE || vh < 0 || vw < 0 || vh > out_h || vw > out_w)
+    return pd_set_error(PD_ERR_INVALID_ARG,
+                        "pd_rle_sample_groups_canvas_u8: bad sizes n=%d n_groups=%d (<= %d) H=%d W=%d window=%dx%d canvas=%dx%d (sides 1..%d)", n,
+                        n_groups, PD_SAMPLE_GROUPS_MAX, H, W, vh, vw, out_h, out_w, PD_CANVAS_MAX_SIDE);
+  if (n == 0 && n_groups == 0) return PD_OK;
+  if ((vh > 0 && vw > 0 && (!src_x || !src_y)) || (n > 0 && (!starts || !offsets || !member_area)) ||
+      (n_groups > 0 && (!group_offsets || !out || !group_area)) || (n > 0 && n_groups > 0 && !group_members))
+    return pd_set_error(PD_ERR_INVALID_ARG, "pd_rle_sample_groups_canvas_u8: null pointer");
+  return launch_sample_groups("pd_rle_sample_groups_canvas_u8", starts, offsets, n, H, src_x, src_y, vh, vw, out_h, out_w, group_offsets,
+                              group_members, n_groups, out, member_area, group_area, (hipStream_t)stream_);
 }
 
 // (x - mean) / std of B same-size planar uint8 images [3, H, W] written straight into the channels-last fp32 batch the backbone reads

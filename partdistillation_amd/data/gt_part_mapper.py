@@ -84,11 +84,13 @@ def group_table(n_obj, part_obj, part_cls, part_ok, merged):
 
 
 def rle_sample_groups(starts, offsets, H, W, src_x, src_y, group_offsets, group_members, out=None, member_area=None, group_area=None,
-                      uploaded=None):
+                      uploaded=None, canvas=None):
     """pd_rle_sample_groups_u8 on device tensors (int32 tables; the group table may be host numpy: its member indices are range-checked
     here, before upload) -> (planes uint8 [G, out_h, out_w], member_area int32 [n], group_area int32 [G]); nothing is pre-zeroed.
     `uploaded`: device int32 copies (group_offsets, group_members padded by one entry) of the host group table the caller has already
-    sent with another upload; the host table is still what is checked"""
+    sent with another upload; the host table is still what is checked.
+    `canvas` = (out_h, out_w): pd_rle_sample_groups_canvas_u8 — the tables span the window len(src_y) x len(src_x) in the top-left corner
+    of each plane and the rest of the plane is 0 (ValueError when the window does not fit)"""
     dev = src_x.device
     n, G = int(offsets.numel()) - 1, len(group_offsets) - 1
     go, gm = (np.asarray(a.cpu() if torch.is_tensor(a) else a, dtype=np.int64).reshape(-1) for a in (group_offsets, group_members))
@@ -102,15 +104,23 @@ def rle_sample_groups(starts, offsets, H, W, src_x, src_y, group_offsets, group_
     else:
         d_go = torch.from_numpy(go.astype(np.int32)).to(dev, non_blocking=True)
         d_gm = torch.from_numpy(np.concatenate((gm, [0])).astype(np.int32)).to(dev, non_blocking=True)  # never a null pointer
-    out_h, out_w = int(src_y.numel()), int(src_x.numel())
+    vh, vw = int(src_y.numel()), int(src_x.numel())
+    out_h, out_w = (vh, vw) if canvas is None else (int(canvas[0]), int(canvas[1]))
+    if vh > out_h or vw > out_w:
+        raise ValueError(f"rle_sample_groups: the window {vh} x {vw} does not fit the canvas {out_h} x {out_w}")
     out = torch.empty((G, out_h, out_w), dtype=torch.uint8, device=dev) if out is None else out
     member_area = torch.empty(n, dtype=torch.int32, device=dev) if member_area is None else member_area
     group_area = torch.empty(G, dtype=torch.int32, device=dev) if group_area is None else group_area
     assert out.is_contiguous() and tuple(out.shape) == (G, out_h, out_w) and member_area.numel() == n and group_area.numel() == G
-    _lib.check(_lib.load().pd_rle_sample_groups_u8(starts.data_ptr() if n else None, offsets.data_ptr() if n else None, n, H, W,
-                                                   src_x.data_ptr(), src_y.data_ptr(), out_h, out_w, d_go.data_ptr(), d_gm.data_ptr(), G,
-                                                   out.data_ptr() if G else None, member_area.data_ptr() if n else None,
-                                                   group_area.data_ptr() if G else None, _lib.current_stream()))
+    tail = (d_go.data_ptr(), d_gm.data_ptr(), G, out.data_ptr() if G else None, member_area.data_ptr() if n else None,
+            group_area.data_ptr() if G else None, _lib.current_stream())
+    if canvas is None:
+        _lib.check(_lib.load().pd_rle_sample_groups_u8(starts.data_ptr() if n else None, offsets.data_ptr() if n else None, n, H, W,
+                                                       src_x.data_ptr(), src_y.data_ptr(), out_h, out_w, *tail))
+    else:
+        _lib.check(_lib.load().pd_rle_sample_groups_canvas_u8(starts.data_ptr() if n else None, offsets.data_ptr() if n else None, n, H, W,
+                                                              src_x.data_ptr() if vw else None, src_y.data_ptr() if vh else None, vh, vw,
+                                                              out_h, out_w, *tail))
     return out, member_area, group_area
 
 

@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("PD_LIB_PATH") or os.path.join(_HERE, "libpd_hip.so") 
 CSRC = os.path.join(_HERE, "csrc")
 
 PD_F32, PD_F64, PD_BF16 = 0, 1, 2
-ABI_VERSION = 46
+ABI_VERSION = 47
 
 _c_int, _c_vp = ctypes.c_int, ctypes.c_void_p
 
@@ -179,6 +179,7 @@ SIGNATURES = {
     "pd_resample_cols_canvas_u8": (_c_int, [_c_vp] + [_c_int] * 3 + [_c_vp] * 3 + [_c_int] * 7 + [_c_vp, _c_vp]),
     "pd_rle_sample_u8": (_c_int, [_c_vp, _c_vp] + [_c_int] * 4 + [_c_vp, _c_vp] + [_c_int] * 3 + [_c_vp, _c_vp, _c_vp]),
     "pd_rle_sample_groups_u8": (_c_int, [_c_vp, _c_vp] + [_c_int] * 3 + [_c_vp, _c_vp] + [_c_int] * 2 + [_c_vp, _c_vp, _c_int] + [_c_vp] * 4),
+    "pd_rle_sample_groups_canvas_u8": (_c_int, [_c_vp, _c_vp] + [_c_int] * 3 + [_c_vp, _c_vp] + [_c_int] * 4 + [_c_vp, _c_vp, _c_int] + [_c_vp] * 4),
     # include/pd_poly.h
     "pd_poly_crossings_i32": (_c_int, [_c_vp, _c_vp] + [_c_int] * 3 + [_c_vp] * 3),
     "pd_sgemm_wgrad_grouped_table_bytes": (ctypes.c_int64, [_c_int]),
