@@ -45,6 +45,7 @@ extern int g_pd_dbg_wgrad_wgs;
 extern int g_pd_dbg_bwd_threads;
 extern int g_pd_dbg_attn_scalar;
 extern int g_pd_dbg_wattn;
+extern int g_pd_dbg_wattn_chunk;
 extern int g_pd_dbg_x3;
 extern int g_pd_dbg_kmeans;
 extern int g_pd_dbg_conv_group_rows;
@@ -92,6 +93,11 @@ extern "C" int pd_debug_set(const char *key, int value)
   if (!strcmp(key, "wgrad_fast")) { pd_dbg_set_wgrad_fast(value); return PD_OK; }
   if (!strcmp(key, "x3_narrow")) { g_pd_dbg_x3_narrow = value; return PD_OK; }
   if (!strcmp(key, "wattn_ablate")) { g_pd_dbg_wattn = value; return PD_OK; }
+  if (!strcmp(key, "wattn_chunk")) {
+    if (value < 0 || value > 8) return pd_set_error(PD_ERR_INVALID_ARG, "pd_debug_set: wattn_chunk is 0 (automatic) or 1..8, got %d", value);
+    g_pd_dbg_wattn_chunk = value;
+    return PD_OK;
+  }
   if (!strcmp(key, "msda_force_generic")) { g_pd_dbg_force_generic = value; return PD_OK; }
   return pd_set_error(PD_ERR_INVALID_ARG, "pd_debug_set: unknown key %s", key);
 }

@@ -33,6 +33,7 @@
 #include "pd_window_attention.h"
 
 int g_pd_dbg_wattn = 0;   // tools/ only: 1 no table gradient at all (its own instantiation), 2 no global flush, 4 skip dK/dV phase, 8 skip dQ phase, 16 skip the table-gradient reduction; forward: 32 loads only, 64 no table staging
+int g_pd_dbg_wattn_chunk = 0;   // pd_debug_set "wattn_chunk" (tests/): 1..8 forces that many windows per workgroup in both directions, 0 = chunk_of
 
 namespace {
 using namespace pdmfma;
@@ -448,7 +449,7 @@ extern "C" int pd_window_attn_fwd_w12(const void *qkv, const float *table, const
   int rc = check(qkv, table, region, win_flags, B_, nW, heads, "pd_window_attn_fwd_w12");
   if (rc || B_ == 0) return rc;
   if (!out || !lse) return pd_set_error(PD_ERR_INVALID_ARG, "pd_window_attn_fwd_w12: null output");
-  const int chunk = chunk_of(B_, heads, 0.2f, 2);
+  const int chunk = g_pd_dbg_wattn_chunk ? g_pd_dbg_wattn_chunk : chunk_of(B_, heads, 0.2f, 2);
   const dim3 grid((B_ + chunk - 1) / chunk, heads);
   hipStream_t s = (hipStream_t)stream_;
   if (region) hipLaunchKernelGGL(wattn_fwd<true>, grid, dim3(THREADS), FWD_LDS, s, (const bf16_t *)qkv, table, region, win_flags, (bf16_t *)out, lse, B_, nW, heads, scale * LOG2E, chunk, (uint8_t *)out_q, (uint8_t *)out_s, q_format, g_pd_dbg_wattn);
@@ -467,7 +468,7 @@ extern "C" int pd_window_attn_bwd_w12(const void *qkv, const float *table, const
   if (!out || !d_out || !lse || !dqkv || !dtable) return pd_set_error(PD_ERR_INVALID_ARG, "pd_window_attn_bwd_w12: null pointer");
   if ((((uintptr_t)out | (uintptr_t)d_out | (uintptr_t)dqkv) & 15) != 0)
     return pd_set_error(PD_ERR_INVALID_ARG, "pd_window_attn_bwd_w12: out / d_out / dqkv must be 16-byte aligned");
-  const int chunk = chunk_of(B_, heads, 1.0f, 1);
+  const int chunk = g_pd_dbg_wattn_chunk ? g_pd_dbg_wattn_chunk : chunk_of(B_, heads, 1.0f, 1);
   const dim3 grid((B_ + chunk - 1) / chunk, heads);
   hipStream_t s = (hipStream_t)stream_;
   static bool attr = false;
