@@ -131,9 +131,14 @@ int pd_gemm_wgrad_f16x2_grouped(const PdGemmWgradDesc *descs, int count, void *t
                                 int64_t workspace_floats, void *stream);
 int pd_conv3x3_wgrad_nhwc_f16x2(const float *dY, const float *X, float *dWk, float *dB, const float *y_amax, const float *x_amax,
                                 float *workspace, int64_t workspace_floats, int B, int H, int W, int Ci, int Co, void *stream);
-/* host-only query (tools / bench.py labels): the kernel pd_gemm_tn_f16x2 takes for a problem — 0 = 128 x 128 tiles, 1 = 256 x 256 tiles,
- * 2 = the row stream (K = 256), 3 = the opt-in register-operand kernel */
-int pd_gemm_tn_f16x2_which(int M, int N, int K, int mode, int has_bits, int has_amax);
+/* host-only query (tests, tools, bench.py labels): the kernel family pd_gemm_tn_f16x2 launches for these arguments (has_*: the pointer is not
+ * NULL; bf16_out: the call is pd_gemm_tn_f16x2_bf16out) under the current pd_debug_set("f16x2_tile") value — the launcher's own decision:
+ *   0 = 128 x 128 tiles (gemm_tn_f16x2)            3 = register operands (gemm_ra_f16x2_k256, probe build only)
+ *   1 = 256 x 256 tiles (gemm_tn_f16x2)            4 = resident accumulators (gemm_kres_f16x2, probe build only)
+ *   2 = the row stream (gemm_rows_f16x2_k256)      5 = producer / consumer wavefronts (gemm_kpc_f16x2)
+ *  -1 = the launcher refuses the problem (sign bits or forced 256 x 256 tiles where N % 256 != 0 or M < 1024) */
+int pd_gemm_tn_f16x2_which(int M, int N, int K, int lda, int ldb, int mode, int has_bits, int has_a_amax, int has_b_amax, int has_c_amax,
+                           int bf16_out);
 
 /* pd_conv3x3_nhwc_f32x3 in the two-plane form: x_amax [B H W] = absolute maxima of X's pixels over their channels, w_amax [Co] =
  * row maxima of Wk (both nullable), y_amax [B H W] (nullable, zero-filled by the caller) receives those of Y.  Ci % 16 == 0. */

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <utility>
 #include <type_traits>
 
 #include "f16x2.h"
@@ -972,16 +973,168 @@ void gemm_kpc_f16x2(const float *__restrict__ A, const float *__restrict__ B, co
 }
 }  // namespace
 
-static const bool g_rows_relu = []() { const char *e = getenv("PD_H2_ROWS_RELU"); return !e || e[0] != '0'; }();   // A/B switch (default on)
-int g_pd_dbg_f16x2 = 0;   // tools/ only (pd_debug_set "f16x2_tile"): see pd_gemm_tn_f16x2
+// ---------------------------------------------------------------------------------------------------------------------------
+// Host side.  Which kernel a problem takes is decided ONCE, by f16x2_plan (pure host code: no HIP call, no static, no environment);
+// the launcher (gemm_tn_f16x2_impl) is a switch on that plan and the label query (pd_gemm_tn_f16x2_which) returns the plan's family.
+//
+// pd_debug_set("f16x2_tile", v): tests and tools/ only, the product runs with 0.  Every form that lost its A/B stays reachable here (the
+// environment switches that once doubled these values were removed when their A/Bs were concluded):
+//   0          DBG_PRODUCT      the product's choice by shape
+//   3 / 13     DBG_WIDE_1 / _2  256 x 256 tiles forced (an error where N % 256 != 0 or M < 1024), one / two register stages, the guarded step
+//   4 / 14     DBG_TILE_1 / _2  128 x 128 tiles forced (sign bits still take the wide tiles), one / two register stages, the guarded step
+//   21         DBG_CONV_KORDER  the 3 x 3 convolution in its (tap, channel) contraction order, the guarded step
+//   61         DBG_ROWS         the row stream where it applies (K = 256, plain epilogue), tiles by shape everywhere else
+//   62         DBG_TILED_RELU   the ReLU epilogues (modes 1 / 2 with sign bits) stay on the tiled kernel, tiles by shape everywhere else
+//   70         DBG_GUARDED      tiles by shape with the guarded step (wide: two register stages, 128 x 128: one); the convolution too
+//   80         DBG_TILED        tiles by shape with the product's step: no row stream for the plain epilogue, no producer / consumer kernel
+//   90         DBG_RA           (probe build) the register-operand kernel; 100 + bits (DBG_RA_ABL ..131): its ablations — bit 1 no A loads,
+//                               2 no fragment reads, 4 no products, 8 no stores, 16 no weight staging
+//   91         DBG_KRES         (probe build) resident accumulators; 200 + bits (DBG_KRES_ABL ..215): ablations of its loop's phases (timing only)
+//   92         DBG_KPC_ANY      the producer / consumer kernel, also for K >= 128 and any number of 256-column panels; (probe build) the 3 x 3
+//                               convolution on it
+//   93         DBG_KPC_PLANES   the producer / consumer kernel, (probe build) with the weights pre-split into planes by one small launch
+//   94         DBG_KPC          the producer / consumer kernel where the product takes it, fp32 weights
+//   220 + bits (DBG_KPC_ABL ..235)  the producer / consumer kernel, (probe build) ablations of the two roles (timing only); 232 stamps
+//                               (pd_debug_read_kpc_trace), 233 stamps without products, 234 (DBG_KPC_PLANES_STAMPS) stamps of the planes form
+// Only 3, 13, 62 and 70 take the ReLU epilogues (modes 1 / 2 with sign bits, K = 256) off the row stream; a value that names no tile rule
+// (21, 90 and above) forces 128 x 128 tiles wherever its kernel does not apply, and outside the probe build (-DPD_PROBES) 90, 91, 100..131 and
+// 200..215 name no kernel at all.
+enum : int {
+  DBG_PRODUCT = 0, DBG_WIDE_1 = 3, DBG_TILE_1 = 4, DBG_WIDE_2 = 13, DBG_TILE_2 = 14, DBG_CONV_KORDER = 21, DBG_ROWS = 61, DBG_TILED_RELU = 62,
+  DBG_GUARDED = 70, DBG_TILED = 80, DBG_RA = 90, DBG_KRES = 91, DBG_KPC_ANY = 92, DBG_KPC_PLANES = 93, DBG_KPC = 94,
+  DBG_RA_ABL = 100, DBG_RA_ABL_END = 132, DBG_KRES_ABL = 200, DBG_KRES_ABL_END = 216, DBG_KPC_ABL = 220, DBG_KPC_PLANES_STAMPS = 234,
+  DBG_KPC_ABL_END = 236
+};
+int g_pd_dbg_f16x2 = DBG_PRODUCT;
+#ifdef PD_PROBES
+constexpr bool kProbes = true;
+#else
+constexpr bool kProbes = false;
+#endif
 
-// the producer / consumer kernel runs ONE 192-row work item per workgroup at a time: a problem with few items (the FPN's res4 input projection:
-// 43 on 256 CUs: 54 us) leaves most of the chip idle.  PD_H2_KPC_MIN_ITEMS=128 sends such problems to the tiled kernel (44-48 us for that launch) —
-// measured over the step on two boxes: 18.19 -> 18.12 ms and 18.54 -> 18.57 ms, i.e. nothing; the default (0) keeps the producer / consumer kernel
-static bool kpc_items_ok(int M, int N)
+static int cu_count()   // of the current device, asked once; 256 where the query fails or answers fewer than 8
 {
-  static const int min_items = []() { const char *e = getenv("PD_H2_KPC_MIN_ITEMS"); return e ? atoi(e) : 0; }();
-  return ((M + KR_RB - 1) / KR_RB) * (N / 256) >= min_items;
+  static const int ncu = []() { int dev = 0, n = 0; (void)hipGetDevice(&dev); return hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n >= 8 ? n : 256; }();
+  return ncu;
+}
+// the persistent grids.  Row stream: one workgroup per CU, the np column panels of a row group on one XCD — whole groups of 8 np workgroups
+// (0: more panels than an XCD has CUs, the kernel does not apply)
+static int rows_grid(int ncu, int np) { return (ncu / (8 * np)) * 8 * np; }
+// resident accumulators / producer - consumer wavefronts: one 192-row x 256-column work item per workgroup at a time
+static int items_grid(int ncu, int64_t M, int np) { const int64_t nwork = (M + KR_RB - 1) / KR_RB * np; return (int)(nwork < ncu ? nwork : ncu); }
+// probe build: the ablation bits (RABL / KABL) whose instantiations exist; with_constant calls f(std::integral_constant<int, V>) for the V equal to v
+using RaAbl = std::integer_sequence<int, 1, 2, 4, 6, 8, 16, 23, 31>;
+using KresAbl = std::integer_sequence<int, 1, 2, 4, 6, 8, 9, 15>;
+using KpcAbl = std::integer_sequence<int, 1, 2, 4, 6, 8, 9, 15, 16, 18>;
+template <int... V> static int among(int v, std::integer_sequence<int, V...>) { return ((v == V) || ...) ? v : 0; }
+template <int... V, typename F> static void with_constant(int v, std::integer_sequence<int, V...>, F f) { ((v == V ? f(std::integral_constant<int, V>{}) : void()), ...); }
+
+enum F16x2Family { F16X2_TILE128 = 0, F16X2_TILE256 = 1, F16X2_ROWS = 2, F16X2_RA = 3, F16X2_KRES = 4, F16X2_KPC = 5 };   // the ids of pd_gemm_tn_f16x2_which
+struct F16x2Plan {
+  F16x2Family family = F16X2_TILE128;
+  bool refuse = false;       // the launcher returns PD_ERR_INVALID_ARG: sign bits or forced wide tiles on a shape the 256 x 256 kernel does not take
+  int nrs = 2, fast = 1;     // tiles: register stages (NRS) and the interleaved interior step (FAST)
+  int ntl = 0;               // register operands: 32-column blocks per workgroup (NTL)
+  int abl = 0;               // probe build: the ablation bits of the kernel (RABL / KABL)
+  bool planes = false;       // probe build, producer / consumer: weights pre-split into planes (BP)
+  int np = 0, grid = 0;      // persistent kernels: 256-column panels and workgroups
+};
+
+static F16x2Plan f16x2_plan(int M, int N, int K, int lda, int ldb, int mode, bool has_bits, bool has_a_amax, bool has_b_amax, bool has_c_amax,
+                            bool bf16_out, int dbg, int ncu)
+{
+  F16x2Plan p;
+  const bool amax_paired = has_a_amax == has_b_amax;           // the persistent kernels scale both operands or neither
+  const bool panels = N > 0 && (N % 256) == 0;
+  p.np = N / 256;
+  // K = 256, plain epilogue: the row stream (gemm_rows_f16x2_k256, see the kernel's header): one persistent workgroup per CU, panels of a row
+  // group on one XCD.  (round 5: the row stream is the product's choice for these shapes again — 22.06 -> 22.00 ms per step in two same-box
+  // A/B pairs, where round 3 measured it 0.2 ms slower; DBG_TILED keeps the tiled kernel)
+  if ((dbg == DBG_PRODUCT || dbg == DBG_ROWS) && !bf16_out && mode == 0 && K == 256 && panels && M >= 8192 && amax_paired && rows_grid(ncu, p.np) > 0) {
+    p.family = F16X2_ROWS, p.grid = rows_grid(ncu, p.np);
+    return p;
+  }
+  // K = 256, plain epilogue: the register-operand kernel (gemm_ra_f16x2_k256) — EXPERIMENTAL, DBG_RA (DBG_RA_ABL + bits: its
+  // ablations).  Correct (tools/probes/test_optin_kernels.py) and SLOWER than the tiled kernel: 35.6 vs 30.4 us at 43 008 x 256 <- 256, 99.6 vs 77.5
+  // at 131 072 rows, 123 vs 91 at N = 1024.  Its ablation (tools/debug/ra_ablate.py, 32 768 rows, one round of 172 workgroups): 8.9 us with every
+  // load, product and store removed (launch + weight staging skeleton), 14.8 with only the C stores, +6 for the A loads, +5 for the weight
+  // staging, +7 for fragments and products — the kernel's phases ADD UP: one 132 KB workgroup per CU, one round, every workgroup stages, loads,
+  // multiplies and stores in step with all the others, so memory is either read or written, never both.  The per-CU share of these shapes
+  // (168 rows x 256 columns) is ~10 us of work under ~20 us of fixed cost, whatever the operand path; see DESIGN.md (round 5).
+  if (kProbes && (dbg == DBG_RA || (dbg >= DBG_RA_ABL && dbg < DBG_RA_ABL_END)) && mode == 0 && K == 256 && M >= 4096 && (N % 32) == 0 && N >= 96 &&
+      amax_paired && ((N % 128) == 0 || (N % 96) == 0)) {
+    p.family = F16X2_RA, p.ntl = (N % 128) == 0 ? 4 : 3;
+    if (p.ntl == 4 && has_a_amax && dbg >= DBG_RA_ABL) p.abl = among(dbg - DBG_RA_ABL, RaAbl{});
+    return p;
+  }
+  // N = 1024 <- K = 256 with the ReLU epilogues (the encoder FFN's first Linear and the input gradient of its second: modes 1 / 2 with sign
+  // bits): the row stream in its own bit order.  The choice depends on (M, N, K) and the debug value only, so the mode-1 launch that writes a
+  // layer's bits and the mode-2 launch that reads them agree.  DBG_TILED_RELU (and the forced wide tiles) keep the tiled kernel.
+  if (dbg != DBG_TILED_RELU && dbg != DBG_WIDE_1 && dbg != DBG_WIDE_2 && dbg != DBG_GUARDED && !bf16_out && (mode == 1 || mode == 2) && has_bits &&
+      K == 256 && panels && N >= 512 && M >= 8192 && has_a_amax && has_b_amax && rows_grid(ncu, p.np) > 0) {
+    p.family = F16X2_ROWS, p.grid = rows_grid(ncu, p.np);
+    return p;
+  }
+  // deep K, 256-column panels, plain epilogue, no row maxima out
+  const bool deep_panels = !bf16_out && mode == 0 && !has_bits && !has_c_amax && (K % KR_KC) == 0 && panels && M >= 8192 && amax_paired;
+  // K outside, a row block's accumulators resident (gemm_kres_f16x2) — EXPERIMENTAL, DBG_KRES (DBG_KRES_ABL + bits: its ablations).  Correct
+  // (tools/probes/test_optin_kernels.py) and NOT faster: 256 <- 1024 at M = 43 008 103 us against the tiled kernel's 92 on the same box (82 vs 85
+  // on another).  tools/debug/kres_ablate.py: 17 us with an empty loop (launch, prologue, the C stores), +27 staging (loads, split, LDS stores,
+  // barrier), +17 fragment reads, +40 products = 101: one 116 KB workgroup per CU, eight wavefronts in step, and the compiler keeps the split's
+  // VALU block out of the matrix instructions' shadow whatever sched_group_barrier asks for, and a hand-ordered stream (sched_barrier between the
+  // pieces, as the kernel has it now) changes nothing: 256 VGPRs leave no room for a second set of fragments, both wavefronts of a SIMD wait for
+  // their LDS reads together — the phases add up.
+  if (kProbes && (dbg == DBG_KRES || (dbg >= DBG_KRES_ABL && dbg < DBG_KRES_ABL_END)) && deep_panels && K >= 512 && N <= 512) {
+    p.family = F16X2_KRES, p.grid = items_grid(ncu, M, p.np);
+    if (has_a_amax && dbg >= DBG_KRES_ABL) p.abl = among(dbg - DBG_KRES_ABL, KresAbl{});
+    return p;
+  }
+  // the same shapes with producer / consumer wavefronts (gemm_kpc_f16x2) — the PRODUCT'S CHOICE since its split uses unpacked VALU instructions
+  // (f16x2.h split4h_u): 256 <- 1024 at M = 43 008 76-78 us against the tiled kernel's 92-94, the step 21.82 -> 21.65 ms (three same-box A/B
+  // pairs).  DBG_TILED keeps the tiled kernel; DBG_KPC_ANY / DBG_KPC_PLANES select it with fp32 weights / pre-split weight planes (not faster
+  // once the split is unpacked: 78.5 vs 77 us).  The kernel's byte offsets are 32-bit: operands below 2^31 bytes.  At least three chunks: the
+  // double-buffered inverse-scale slot is reused two chunks later.
+  // The kernel runs ONE 192-row work item per workgroup at a time: a problem with few items (the FPN's res4 input projection: 43 on 256 CUs:
+  // 54 us) leaves most of the chip idle.  Sending problems of fewer than 128 items to the tiled kernel (44-48 us for that launch) was measured
+  // over the step on two boxes: 18.19 -> 18.12 ms and 18.54 -> 18.57 ms, i.e. nothing: no such threshold.
+  if ((dbg == DBG_PRODUCT || dbg == DBG_KPC_ANY || dbg == DBG_KPC_PLANES || dbg == DBG_KPC || (dbg >= DBG_KPC_ABL && dbg < DBG_KPC_ABL_END)) && deep_panels &&
+      (int64_t)M * lda * 4 < (1ll << 31) && (int64_t)N * ldb * 4 < (1ll << 31) && (K >= 512 || (dbg == DBG_KPC_ANY && K >= 128)) && K / KR_KC >= 3 &&
+      (N <= 512 || dbg == DBG_KPC_ANY)) {
+    p.family = F16X2_KPC, p.grid = items_grid(ncu, M, p.np);
+    if (kProbes && has_a_amax && dbg >= DBG_KPC_ABL && dbg != DBG_KPC_PLANES_STAMPS)
+      p.abl = dbg == DBG_KPC_ABL + 12 ? 16 : dbg == DBG_KPC_ABL + 13 ? 18 : among(dbg - DBG_KPC_ABL, KpcAbl{});
+    else if (kProbes && (dbg == DBG_KPC_PLANES || dbg == DBG_KPC_PLANES_STAMPS))
+      p.planes = true, p.abl = dbg == DBG_KPC_PLANES_STAMPS ? 16 : 0;
+    return p;
+  }
+  // the tiled kernel.  The sign bits are laid out in the 256 x 256 kernel's accumulator order: bits / mask launches must take that kernel.
+  // (256 x 256 tiles for N < 1024, K >= 512: faster in isolation (256 <- 1024: 80.7 vs 96.8 us), 0.15 ms SLOWER over the step (round 5 A/B:
+  // 22.01 vs 21.86 ms): not taken.)
+  // Measured and dropped (tools/bench_gemm_h2.py, M = 43 008): 32-deep steps (1024 <- 256 103.7 vs 96.8 us, 256 <- 1024 90.9 vs 85.4,
+  // 256 <- 256 32.9 vs 29.3: half the workgroups in flight), 128 x 256 tiles with two workgroups per CU (no gain).
+  // Two register stages (loads two steps ahead of their split): 97.0 vs 99.9 us on 1024 <- 256, 85.3 vs 87.9 on 256 <- 1024.
+  // Interior workgroups take the branch-free, interleaved step (FAST = 1): 1024 <- 256 109 -> 92 us, 256 <- 1024 91 -> 79 us (wide tiles),
+  // 256 <- 1024 94 -> 87 us (128 x 128 tiles) at M = 43 520; the step 24.9 -> 24.65 ms.
+  // (measured and dropped, round 6: 32-deep steps for the few-tile, long-contraction problems — the FPN's res5 input projection, 32 tiles x 128
+  //  steps of 16: 70 us — run 76.6 us)
+  const bool wide_ok = (N % 256) == 0 && M >= 1024;
+  const bool by_shape = dbg == DBG_PRODUCT || dbg == DBG_ROWS || dbg == DBG_GUARDED || dbg == DBG_TILED || dbg == DBG_TILED_RELU;
+  if (has_bits || dbg == DBG_WIDE_1 || dbg == DBG_WIDE_2 || (by_shape && wide_ok && (int64_t)((M + 255) / 256) * (N / 256) >= 128 && N >= 1024)) {
+    p.family = F16X2_TILE256, p.refuse = !wide_ok;
+    p.nrs = dbg == DBG_WIDE_1 ? 1 : 2, p.fast = !(dbg == DBG_WIDE_1 || dbg == DBG_WIDE_2 || dbg == DBG_GUARDED);
+  } else {
+    p.nrs = (dbg == DBG_TILE_1 || dbg == DBG_GUARDED) ? 1 : 2, p.fast = !(dbg == DBG_TILE_1 || dbg == DBG_TILE_2 || dbg == DBG_GUARDED);
+  }
+  return p;
+}
+
+// kernels with more than 64 KB of dynamic LDS have to be allowed it once, before the first launch of each instantiation
+template <auto KERNEL, typename... Args>
+static void launch_lds(int grid, int threads, size_t lds, hipStream_t st, Args... args)
+{
+  static const hipError_t allowed = hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  (void)allowed;
+  hipLaunchKernelGGL(KERNEL, dim3((unsigned)grid), dim3((unsigned)threads), lds, st, args...);
 }
 
 template <int TM, int TN, int WN, int BKK, bool CONV = false, int NRS = 1, int FAST = 0>
@@ -1002,7 +1155,7 @@ static int launch_f16x2(const float *A, const float *B, const float *bias, float
   static bool attr[3] = {false, false, false};
   if (!attr[mode]) { (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr[mode] = true; }
   hipLaunchKernelGGL(k, dim3((unsigned)((int64_t)tm * tn)), dim3(NTH), lds, st, A, B, bias, C, M, N, K, lda, ldb, ldc, tn, bits, colsum, a_amax,
-                     b_amax, reinterpret_cast<unsigned *>(c_amax), H, W, g_pd_dbg_f16x2 == 21 ? 0 : 1);
+                     b_amax, reinterpret_cast<unsigned *>(c_amax), H, W, g_pd_dbg_f16x2 == DBG_CONV_KORDER ? 0 : 1);
   return pd_check_launch("pd_gemm_tn_f16x2");
 }
 
@@ -1028,245 +1181,94 @@ static int gemm_tn_f16x2_impl(const float *A, const float *B, const float *bias,
   if ((K & 3) || (lda & 3) || (ldb & 3) || ((uintptr_t)A & 15) || ((uintptr_t)B & 15))
     return pd_set_error(PD_ERR_INVALID_ARG, "pd_gemm_tn_f16x2: K, lda, ldb must be multiples of 4 and A, B 16-byte aligned");
   hipStream_t st = (hipStream_t)stream_;
-  const int dbg = g_pd_dbg_f16x2;
-  // (round 5: the row stream is the product's choice for these shapes again — 22.06 -> 22.00 ms per step in two same-box A/B pairs, where round 3
-  // measured it 0.2 ms slower; PD_H2_ROWS_K256=0 / pd_debug_set("f16x2_tile", 80) keep the tiled kernel)
-  static const bool rows_k256 = []() { const char *e = getenv("PD_H2_ROWS_K256"); return !e || e[0] != '0'; }();
-  if ((dbg == 61 || (rows_k256 && dbg == 0)) && !flags && mode == 0 && K == 256 && (N % 256) == 0 && M >= 8192 && (a_amax == nullptr) == (b_amax == nullptr)) {
-    // row stream (gemm_rows_f16x2_k256, experimental: see the kernel's header): one persistent workgroup per CU, panels of a row group on one XCD
-    static int ncu = 0;
-    if (!ncu) { int dev = 0; (void)hipGetDevice(&dev); if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu < 8) ncu = 256; }
-    const int np = N / 256, G = (ncu / (8 * np)) * 8 * np;
-    if (G > 0) {
-      if (a_amax)
-        hipLaunchKernelGGL(gemm_rows_f16x2_k256<true>, dim3((unsigned)G), dim3(512), 0, st, A, B, bias, C, M, np, lda, ldb, ldc, a_amax, b_amax,
-                           reinterpret_cast<unsigned *>(c_amax));
-      else
-        hipLaunchKernelGGL(gemm_rows_f16x2_k256<false>, dim3((unsigned)G), dim3(512), 0, st, A, B, bias, C, M, np, lda, ldb, ldc, a_amax, b_amax,
-                           reinterpret_cast<unsigned *>(c_amax));
-      return pd_check_launch("pd_gemm_tn_f16x2 (row stream)");
+  const F16x2Plan p = f16x2_plan(M, N, K, lda, ldb, mode, bits != nullptr, a_amax != nullptr, b_amax != nullptr, c_amax != nullptr, flags != 0,
+                                 g_pd_dbg_f16x2, cu_count());
+  switch (p.family) {
+    case F16X2_ROWS: {
+#define ROWS(AM, MODE, ...) hipLaunchKernelGGL((gemm_rows_f16x2_k256<AM, MODE>), dim3((unsigned)p.grid), dim3(512), 0, st, A, B, bias, C, M, p.np, lda, ldb, ldc, \
+                                               a_amax, b_amax, reinterpret_cast<unsigned *>(c_amax), ##__VA_ARGS__)
+      if (mode == 1) ROWS(true, 1, reinterpret_cast<unsigned short *>(bits), colsum);
+      else if (mode == 2) ROWS(true, 2, reinterpret_cast<unsigned short *>(bits), colsum);
+      else if (a_amax) ROWS(true, 0);
+      else ROWS(false, 0);
+#undef ROWS
+      return pd_check_launch(mode ? "pd_gemm_tn_f16x2 (row stream, ReLU epilogue)" : "pd_gemm_tn_f16x2 (row stream)");
     }
-  }
 #ifdef PD_PROBES
-  // K = 256, plain epilogue: the register-operand kernel (gemm_ra_f16x2_k256) — EXPERIMENTAL, pd_debug_set("f16x2_tile", 90) (100 + bits: its
-  // ablations).  Correct (tests/test_gemm_gpu.py) and SLOWER than the tiled kernel: 35.6 vs 30.4 us at 43 008 x 256 <- 256, 99.6 vs 77.5 at 131 072
-  // rows, 123 vs 91 at N = 1024.  Its ablation (tools/debug/ra_ablate.py, 32 768 rows, one round of 172 workgroups): 8.9 us with every load,
-  // product and store removed (launch + weight staging skeleton), 14.8 with only the C stores, +6 for the A loads, +5 for the weight staging,
-  // +7 for fragments and products — the kernel's phases ADD UP: one 132 KB workgroup per CU, one round, every workgroup stages, loads,
-  // multiplies and stores in step with all the others, so memory is either read or written, never both.  The per-CU share of these shapes
-  // (168 rows x 256 columns) is ~10 us of work under ~20 us of fixed cost, whatever the operand path; see DESIGN.md (round 5).
-  if ((dbg == 90 || (dbg >= 100 && dbg < 132)) && mode == 0 && K == 256 && M >= 4096 && (N % 32) == 0 && N >= 96 &&
-      (a_amax == nullptr) == (b_amax == nullptr)) {
-    const int ntl = (N % 128) == 0 ? 4 : (N % 96) == 0 ? 3 : 0;
-    if (ntl) {
+    case F16X2_RA: {
       constexpr int NWV = 12;
-      const int nblk_n = N / (ntl * 32), nblk_m = (M + NWV * 32 - 1) / (NWV * 32);
-      const size_t lds = (size_t)2 * 32 * (ntl * 32 * 16 + RA_PSTRIDE_PAD) + (size_t)(ntl * 32 + NWV * 32) * sizeof(float);
-      typedef void (*rfn)(const float *, const float *, const float *, float *, int, int, int, int, int, int, const float *, const float *, unsigned *, int);
-      rfn kf = ntl == 4 ? (a_amax ? (rfn)gemm_ra_f16x2_k256<4, NWV, true> : (rfn)gemm_ra_f16x2_k256<4, NWV, false>)
-                        : (a_amax ? (rfn)gemm_ra_f16x2_k256<3, NWV, true> : (rfn)gemm_ra_f16x2_k256<3, NWV, false>);
-      if (ntl == 4 && a_amax && dbg >= 100 && dbg < 132) {             // tools: ablations (bit 1 no A loads, 2 no fragment reads, 4 no products, 8 no stores, 16 no weight staging)
-        switch (dbg - 100) {
-          case 1: kf = (rfn)gemm_ra_f16x2_k256<4, NWV, true, 1>; break;
-          case 2: kf = (rfn)gemm_ra_f16x2_k256<4, NWV, true, 2>; break;
-          case 4: kf = (rfn)gemm_ra_f16x2_k256<4, NWV, true, 4>; break;
-          case 6: kf = (rfn)gemm_ra_f16x2_k256<4, NWV, true, 6>; break;
-          case 8: kf = (rfn)gemm_ra_f16x2_k256<4, NWV, true, 8>; break;
-          case 16: kf = (rfn)gemm_ra_f16x2_k256<4, NWV, true, 16>; break;
-          case 31: kf = (rfn)gemm_ra_f16x2_k256<4, NWV, true, 31>; break;
-          case 23: kf = (rfn)gemm_ra_f16x2_k256<4, NWV, true, 23>; break;
-          default: break;
-        }
-        (void)hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      }
-      static bool rattr[4] = {false, false, false, false};
-      const int ai = (ntl == 4 ? 0 : 2) + (a_amax ? 1 : 0);
-      if (!rattr[ai]) { (void)hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); rattr[ai] = true; }
-      hipLaunchKernelGGL(kf, dim3((unsigned)(nblk_m * nblk_n)), dim3(NWV * 64), lds, st, A, B, bias, C, M, N, lda, ldb, ldc, nblk_n, a_amax, b_amax,
-                         reinterpret_cast<unsigned *>(c_amax), flags);
+      const int nblk_n = N / (p.ntl * 32), nblk_m = (M + NWV * 32 - 1) / (NWV * 32);
+      const size_t lds = (size_t)2 * 32 * (p.ntl * 32 * 16 + RA_PSTRIDE_PAD) + (size_t)(p.ntl * 32 + NWV * 32) * sizeof(float);
+#define RA(NTL, AM, ABL) launch_lds<gemm_ra_f16x2_k256<NTL, NWV, AM, ABL>>(nblk_m * nblk_n, NWV * 64, lds, st, A, B, bias, C, M, N, lda, ldb, ldc, nblk_n, a_amax, \
+                                                                           b_amax, reinterpret_cast<unsigned *>(c_amax), flags)
+      if (p.abl) with_constant(p.abl, RaAbl{}, [&](auto abl) { RA(4, true, decltype(abl)::value); });
+      else if (p.ntl == 4) { if (a_amax) RA(4, true, 0); else RA(4, false, 0); }
+      else { if (a_amax) RA(3, true, 0); else RA(3, false, 0); }
+#undef RA
       return pd_check_launch("pd_gemm_tn_f16x2 (register operands)");
     }
-  }
-#endif
-  // N = 1024 <- K = 256 with the ReLU epilogues (the encoder FFN's first Linear and the input gradient of its second: modes 1 / 2 with sign
-  // bits): the row stream in its own bit order.  The choice depends on (M, N, K) and the switches only, so the mode-1 launch that writes a
-  // layer's bits and the mode-2 launch that reads them agree.  pd_debug_set("f16x2_tile", 62) / PD_H2_ROWS_RELU=0 keep the tiled kernel.
-  if (dbg != 62 && dbg != 3 && dbg != 13 && dbg != 70 && !flags && (mode == 1 || mode == 2) && bits && K == 256 && (N % 256) == 0 && N >= 512 && M >= 8192 &&
-      a_amax && b_amax && g_rows_relu) {
-    static int ncu2 = 0;
-    if (!ncu2) { int dev = 0; (void)hipGetDevice(&dev); if (hipDeviceGetAttribute(&ncu2, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu2 < 8) ncu2 = 256; }
-    const int np = N / 256, G = (ncu2 / (8 * np)) * 8 * np;
-    if (G > 0) {
-      if (mode == 1)
-        hipLaunchKernelGGL((gemm_rows_f16x2_k256<true, 1>), dim3((unsigned)G), dim3(512), 0, st, A, B, bias, C, M, np, lda, ldb, ldc, a_amax, b_amax,
-                           reinterpret_cast<unsigned *>(c_amax), reinterpret_cast<unsigned short *>(bits), colsum);
-      else
-        hipLaunchKernelGGL((gemm_rows_f16x2_k256<true, 2>), dim3((unsigned)G), dim3(512), 0, st, A, B, bias, C, M, np, lda, ldb, ldc, a_amax, b_amax,
-                           reinterpret_cast<unsigned *>(c_amax), reinterpret_cast<unsigned short *>(bits), colsum);
-      return pd_check_launch("pd_gemm_tn_f16x2 (row stream, ReLU epilogue)");
+    case F16X2_KRES: {
+#define KRES(AM, ABL) launch_lds<gemm_kres_f16x2<AM, ABL>>(p.grid, 512, KR_LDS, st, A, B, bias, C, M, K, lda, ldb, ldc, p.np, a_amax, b_amax)
+      if (p.abl) with_constant(p.abl, KresAbl{}, [&](auto abl) { KRES(true, decltype(abl)::value); });
+      else if (a_amax) KRES(true, 0);
+      else KRES(false, 0);
+#undef KRES
+      return pd_check_launch("pd_gemm_tn_f16x2 (resident accumulators)");
     }
-  }
+#endif
+    case F16X2_KPC: {
+#define KPC(AM, ABL, BP, WEIGHTS) launch_lds<gemm_kpc_f16x2<AM, ABL, BP>>(p.grid, 768, KP_LDS, st, A, WEIGHTS, bias, C, M, K, lda, ldb, ldc, p.np, a_amax, b_amax, 0, 0)
 #ifdef PD_PROBES
-  // deep K, 256-column panels, plain epilogue: K outside, a row block's accumulators resident (gemm_kres_f16x2) — EXPERIMENTAL, opt-in
-  // (PD_H2_KRES=1 / pd_debug_set("f16x2_tile", 91); 200 + bits: its ablations).  Correct (tests/test_gemm_gpu.py) and NOT faster: 256 <- 1024 at
-  // M = 43 008 103 us against the tiled kernel's 92 on the same box (82 vs 85 on another).  tools/debug/kres_ablate.py: 17 us with an empty
-  // loop (launch, prologue, the C stores), +27 staging (loads, split, LDS stores, barrier), +17 fragment reads, +40 products = 101: one
-  // 116 KB workgroup per CU, eight wavefronts in step, and the compiler keeps the split's VALU block out of the matrix instructions' shadow
-  // whatever sched_group_barrier asks for, and a hand-ordered stream (sched_barrier between the pieces, as the kernel has it now) changes nothing:
-  // 256 VGPRs leave no room for a second set of fragments, both wavefronts of a SIMD wait for their LDS reads together — the phases add up.
-  static const bool kres_env = []() { const char *e = getenv("PD_H2_KRES"); return e && e[0] == '1'; }();
-  if (((kres_env && dbg == 0) || dbg == 91 || (dbg >= 200 && dbg < 216)) && !flags && mode == 0 && !bits && !c_amax && K >= 512 && (K % KR_KC) == 0 && (N % 256) == 0 && N <= 512 && M >= 8192 &&
-      (a_amax == nullptr) == (b_amax == nullptr)) {
-    static int ncu3 = 0;
-    if (!ncu3) { int dev = 0; (void)hipGetDevice(&dev); if (hipDeviceGetAttribute(&ncu3, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu3 < 8) ncu3 = 256; }
-    const int np = N / 256, nwork = ((M + KR_RB - 1) / KR_RB) * np, G = nwork < ncu3 ? nwork : ncu3;
-    static bool kattr = false;
-    if (!kattr) {
-      (void)hipFuncSetAttribute((const void *)gemm_kres_f16x2<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)KR_LDS);
-      (void)hipFuncSetAttribute((const void *)gemm_kres_f16x2<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)KR_LDS);
-      kattr = true;
-    }
-    if (a_amax && dbg >= 200 && dbg < 216) {                           // tools: ablations of the loop's phases (timing only)
-      typedef void (*kfn2)(const float *, const float *, const float *, float *, int, int, int, int, int, int, const float *, const float *);
-      kfn2 kf = nullptr;
-      switch (dbg - 200) {
-        case 1: kf = gemm_kres_f16x2<true, 1>; break;
-        case 2: kf = gemm_kres_f16x2<true, 2>; break;
-        case 4: kf = gemm_kres_f16x2<true, 4>; break;
-        case 6: kf = gemm_kres_f16x2<true, 6>; break;
-        case 8: kf = gemm_kres_f16x2<true, 8>; break;
-        case 9: kf = gemm_kres_f16x2<true, 9>; break;
-        case 15: kf = gemm_kres_f16x2<true, 15>; break;
-        default: kf = gemm_kres_f16x2<true, 0>; break;
+      if (p.planes) {
+        // weights pre-split into planes by one small launch (a per-process scratch: launches of one stream are ordered)
+        static unsigned short *planes = nullptr;
+        static int64_t planes_cap = 0;
+        const int64_t need = (int64_t)2 * N * K;
+        if (need > planes_cap) {
+          if (planes) (void)hipFree(planes);
+          if (hipMalloc(reinterpret_cast<void **>(&planes), (size_t)need * 2) != hipSuccess) { planes = nullptr; planes_cap = 0; return pd_set_error(PD_ERR_LAUNCH, "pd_gemm_tn_f16x2: no memory for the weight planes"); }
+          planes_cap = need;
+        }
+        hipLaunchKernelGGL(split_planes_f16x2, dim3((unsigned)(((int64_t)N * (K / 4) + 255) / 256)), dim3(256), 0, st, B, ldb, b_amax, planes, N, K);
+        const float *bpl = reinterpret_cast<const float *>(planes);
+        if (p.abl == 16) KPC(true, 16, true, bpl);
+        else if (a_amax) KPC(true, 0, true, bpl);
+        else KPC(false, 0, true, bpl);
+        return pd_check_launch("pd_gemm_tn_f16x2 (producer / consumer wavefronts, weight planes)");
       }
-      (void)hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)KR_LDS);
-      hipLaunchKernelGGL(kf, dim3((unsigned)G), dim3(512), KR_LDS, st, A, B, bias, C, M, K, lda, ldb, ldc, np, a_amax, b_amax);
-      return pd_check_launch("pd_gemm_tn_f16x2 (resident accumulators, ablation)");
-    }
-    if (a_amax) hipLaunchKernelGGL(gemm_kres_f16x2<true>, dim3((unsigned)G), dim3(512), KR_LDS, st, A, B, bias, C, M, K, lda, ldb, ldc, np, a_amax, b_amax);
-    else hipLaunchKernelGGL(gemm_kres_f16x2<false>, dim3((unsigned)G), dim3(512), KR_LDS, st, A, B, bias, C, M, K, lda, ldb, ldc, np, a_amax, b_amax);
-    return pd_check_launch("pd_gemm_tn_f16x2 (resident accumulators)");
-  }
+      if (p.abl) {
+        with_constant(p.abl, KpcAbl{}, [&](auto abl) { KPC(true, decltype(abl)::value, false, B); });
+        return pd_check_launch("pd_gemm_tn_f16x2 (producer / consumer wavefronts, ablation)");
+      }
 #endif
-  // the same shapes with producer / consumer wavefronts (gemm_kpc_f16x2) — the PRODUCT'S CHOICE since its split uses unpacked VALU instructions
-  // (f16x2.h split4h_u): 256 <- 1024 at M = 43 008 76-78 us against the tiled kernel's 92-94, the step 21.82 -> 21.65 ms (three same-box A/B pairs).
-  // PD_H2_KPC=0 / pd_debug_set("f16x2_tile", 80) keep the tiled kernel; 92 / 93 select it with fp32 weights / pre-split weight planes.
-  static const bool kpc_env = []() { const char *e = getenv("PD_H2_KPC"); return !e || e[0] != '0'; }();
-  if (((kpc_env && dbg == 0) || dbg == 92 || dbg == 93 || dbg == 94 || (dbg >= 220 && dbg < 236)) && (int64_t)M * lda * 4 < (1ll << 31) && (int64_t)N * ldb * 4 < (1ll << 31) && !flags && mode == 0 && !bits && !c_amax && (K >= 512 || (dbg == 92 && K >= 128)) && (K % KR_KC) == 0 && K / KR_KC >= 3 /* the double-buffered inverse-scale slot is reused two chunks later */ && (N % 256) == 0 && (N <= 512 || dbg == 92) && M >= 8192 && kpc_items_ok(M, N) &&
-      (a_amax == nullptr) == (b_amax == nullptr)) {
-    static int ncu4 = 0;
-    if (!ncu4) { int dev = 0; (void)hipGetDevice(&dev); if (hipDeviceGetAttribute(&ncu4, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu4 < 8) ncu4 = 256; }
-    const int np = N / 256, nwork = ((M + KR_RB - 1) / KR_RB) * np, G = nwork < ncu4 ? nwork : ncu4;
-    static bool pattr = false;
-    if (!pattr) {
-      (void)hipFuncSetAttribute((const void *)gemm_kpc_f16x2<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)KP_LDS);
-      (void)hipFuncSetAttribute((const void *)gemm_kpc_f16x2<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)KP_LDS);
-      pattr = true;
+      if (a_amax) KPC(true, 0, false, B);
+      else KPC(false, 0, false, B);
+#undef KPC
+      return pd_check_launch("pd_gemm_tn_f16x2 (producer / consumer wavefronts)");
     }
-#ifdef PD_PROBES
-    if (a_amax && dbg >= 220 && dbg < 236 && dbg != 234) {             // tools: ablations of the two roles (timing only); 234: stamps of the planes form, below
-      typedef void (*kfn3)(const float *, const float *, const float *, float *, int, int, int, int, int, int, const float *, const float *, int, int);
-      kfn3 kf = nullptr;
-      switch (dbg - 220) {
-        case 1: kf = gemm_kpc_f16x2<true, 1>; break;
-        case 2: kf = gemm_kpc_f16x2<true, 2>; break;
-        case 4: kf = gemm_kpc_f16x2<true, 4>; break;
-        case 6: kf = gemm_kpc_f16x2<true, 6>; break;
-        case 8: kf = gemm_kpc_f16x2<true, 8>; break;
-        case 9: kf = gemm_kpc_f16x2<true, 9>; break;
-        case 15: kf = gemm_kpc_f16x2<true, 15>; break;
-        case 12: kf = gemm_kpc_f16x2<true, 16>; break;        // 232: stamps (pd_debug_read_kpc_trace)
-        case 13: kf = gemm_kpc_f16x2<true, 18>; break;        // 233: stamps, no products
-        default: kf = gemm_kpc_f16x2<true, 0>; break;
-      }
-      (void)hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)KP_LDS);
-      hipLaunchKernelGGL(kf, dim3((unsigned)G), dim3(768), KP_LDS, st, A, B, bias, C, M, K, lda, ldb, ldc, np, a_amax, b_amax, 0, 0);
-      return pd_check_launch("pd_gemm_tn_f16x2 (producer / consumer wavefronts, ablation)");
-    }
-    static const bool kpc_bp = []() { const char *e = getenv("PD_H2_KPC_PLANES"); return e && e[0] == '1'; }();   // (not faster once the split is unpacked: 78.5 vs 77 us)
-    if ((kpc_bp && dbg != 94 && dbg != 92) || dbg == 93 || dbg == 234) {
-      // weights pre-split into planes by one small launch (a per-process scratch: launches of one stream are ordered)
-      static unsigned short *planes = nullptr;
-      static int64_t planes_cap = 0;
-      const int64_t need = (int64_t)2 * N * K;
-      if (need > planes_cap) {
-        if (planes) (void)hipFree(planes);
-        if (hipMalloc(reinterpret_cast<void **>(&planes), (size_t)need * 2) != hipSuccess) { planes = nullptr; planes_cap = 0; return pd_set_error(PD_ERR_LAUNCH, "pd_gemm_tn_f16x2: no memory for the weight planes"); }
-        planes_cap = need;
-      }
-      hipLaunchKernelGGL(split_planes_f16x2, dim3((unsigned)(((int64_t)N * (K / 4) + 255) / 256)), dim3(256), 0, st, B, ldb, b_amax, planes, N, K);
-      static bool battr = false;
-      if (!battr) {
-        (void)hipFuncSetAttribute((const void *)(gemm_kpc_f16x2<true, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)KP_LDS);
-        (void)hipFuncSetAttribute((const void *)(gemm_kpc_f16x2<false, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)KP_LDS);
-        (void)hipFuncSetAttribute((const void *)(gemm_kpc_f16x2<true, 16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)KP_LDS);
-        battr = true;
-      }
-      const float *bpl = reinterpret_cast<const float *>(planes);
-      if (dbg == 234) hipLaunchKernelGGL((gemm_kpc_f16x2<true, 16, true>), dim3((unsigned)G), dim3(768), KP_LDS, st, A, bpl, bias, C, M, K, lda, ldb, ldc, np, a_amax, b_amax, 0, 0);
-      else if (a_amax) hipLaunchKernelGGL((gemm_kpc_f16x2<true, 0, true>), dim3((unsigned)G), dim3(768), KP_LDS, st, A, bpl, bias, C, M, K, lda, ldb, ldc, np, a_amax, b_amax, 0, 0);
-      else hipLaunchKernelGGL((gemm_kpc_f16x2<false, 0, true>), dim3((unsigned)G), dim3(768), KP_LDS, st, A, bpl, bias, C, M, K, lda, ldb, ldc, np, a_amax, b_amax, 0, 0);
-      return pd_check_launch("pd_gemm_tn_f16x2 (producer / consumer wavefronts, weight planes)");
-    }
-#endif
-    if (a_amax) hipLaunchKernelGGL(gemm_kpc_f16x2<true>, dim3((unsigned)G), dim3(768), KP_LDS, st, A, B, bias, C, M, K, lda, ldb, ldc, np, a_amax, b_amax, 0, 0);
-    else hipLaunchKernelGGL(gemm_kpc_f16x2<false>, dim3((unsigned)G), dim3(768), KP_LDS, st, A, B, bias, C, M, K, lda, ldb, ldc, np, a_amax, b_amax, 0, 0);
-    return pd_check_launch("pd_gemm_tn_f16x2 (producer / consumer wavefronts)");
-  }
-  // the sign bits are laid out in the 256 x 256 kernel's accumulator order: bits / mask launches must take that kernel
-  const bool need_wide = bits != nullptr;
-  if (need_wide && ((N % 256) || M < 1024)) return pd_set_error(PD_ERR_INVALID_ARG, "pd_gemm_tn_f16x2: sign bits need N %% 256 == 0 and M >= 1024");
-  const bool wide_ok = (N % 256) == 0 && M >= 1024;
-  const bool by_shape = dbg == 0 || dbg == 61 || dbg == 70 || dbg == 80 || dbg == 62;
-  static const bool wide_deepk = []() { const char *e = getenv("PD_H2_WIDE_DEEPK"); return e && e[0] == '1'; }();   // 256 x 256 tiles for N < 1024, K >= 512: faster in isolation (256 <- 1024: 80.7 vs 96.8 us), 0.15 ms SLOWER over the step (round 5 A/B: 22.01 vs 21.86 ms): off; PD_H2_WIDE_DEEPK=1 restores
-  const bool wide = need_wide || dbg == 3 || dbg == 13 || (by_shape && wide_ok && (int64_t)((M + 255) / 256) * (N / 256) >= 128 && (N >= 1024 || (K >= 512 && wide_deepk)));
-  static const bool fast_env = []() { const char *e = getenv("PD_H2_FAST"); return !e || e[0] != '0'; }();   // A/B switch: the interleaved interior step
 #define GO(TM, TN, WN, NRS, FAST) return launch_f16x2<TM, TN, WN, 16, false, NRS, FAST>(A, B, bias, C, M, N, K, lda, ldb, ldc, mode, bits, colsum, a_amax, b_amax, c_amax, st, flags)
-  // Measured and dropped (tools/bench_gemm_h2.py, M = 43 008): 32-deep steps (1024 <- 256 103.7 vs 96.8 us, 256 <- 1024 90.9 vs 85.4,
-  // 256 <- 256 32.9 vs 29.3: half the workgroups in flight), 128 x 256 tiles with two workgroups per CU (no gain).
-  // Two register stages (loads two steps ahead of their split): 97.0 vs 99.9 us on 1024 <- 256, 85.3 vs 87.9 on 256 <- 1024.
-  // Interior workgroups take the branch-free, interleaved step (FAST = 1): 1024 <- 256 109 -> 92 us, 256 <- 1024 91 -> 79 us (wide tiles),
-  // 256 <- 1024 94 -> 87 us (128 x 128 tiles) at M = 43 520; the step 24.9 -> 24.65 ms.
-  // pd_debug_set("f16x2_tile"): 3 / 13 wide tiles with one / two register stages and the guarded step, 4 / 14 the same for 128 x 128
-  // tiles, 70 the guarded step by shape, 61 the row stream where it applies, 21 the (tap, channel) contraction order of the convolution
-  if (wide) {
-    if (!wide_ok) return pd_set_error(PD_ERR_INVALID_ARG, "pd_gemm_tn_f16x2: 256 x 256 tiles need N %% 256 == 0 and M >= 1024");
-    if (dbg == 3) GO(256, 256, 128, 1, 0);
-    if (dbg == 13 || dbg == 70) GO(256, 256, 128, 2, 0);
-    if (!fast_env) GO(256, 256, 128, 2, 0);
-    GO(256, 256, 128, 2, 1);
-  }
-  // (measured and dropped, round 6: 32-deep steps for the few-tile, long-contraction problems — the FPN's res5 input projection, 32 tiles x 128
-  //  steps of 16: 70 us — run 76.6 us)
-  if (dbg == 4 || dbg == 70) GO(128, 128, 64, 1, 0);
-  if (dbg == 14 || !fast_env) GO(128, 128, 64, 2, 0);
-  GO(128, 128, 64, 2, 1);
+    case F16X2_TILE256:
+      if (p.refuse)
+        return pd_set_error(PD_ERR_INVALID_ARG, bits ? "pd_gemm_tn_f16x2: sign bits need N %% 256 == 0 and M >= 1024" : "pd_gemm_tn_f16x2: 256 x 256 tiles need N %% 256 == 0 and M >= 1024");
+      if (p.nrs == 1) GO(256, 256, 128, 1, 0);
+      if (!p.fast) GO(256, 256, 128, 2, 0);
+      GO(256, 256, 128, 2, 1);
+    default:                                                         // F16X2_TILE128
+      if (p.nrs == 1) GO(128, 128, 64, 1, 0);
+      if (!p.fast) GO(128, 128, 64, 2, 0);
+      GO(128, 128, 64, 2, 1);
 #undef GO
+  }
 }
 
-// which kernel pd_gemm_tn_f16x2 launches for a problem (tools / bench.py labels): 0 = 128 x 128 tiles, 1 = 256 x 256 tiles, 2 = the row stream
-// (gemm_rows_f16x2_k256), 3 = the register-operand kernel (opt-in), 4 = resident accumulators (gemm_kres_f16x2, opt-in), 5 = the same with
-// producer / consumer wavefronts (gemm_kpc_f16x2; a launch that asks for output row maxima takes the tiled kernel).  Mirrors the dispatch of gemm_tn_f16x2_impl.
-extern "C" int pd_gemm_tn_f16x2_which(int M, int N, int K, int mode, int has_bits, int has_amax)
+// the kernel family pd_gemm_tn_f16x2 (bf16_out: pd_gemm_tn_f16x2_bf16out) launches for a problem under the current debug value: f16x2_plan's
+// answer, -1 where the launcher refuses the problem (include/pd_gemm.h lists the ids)
+extern "C" int pd_gemm_tn_f16x2_which(int M, int N, int K, int lda, int ldb, int mode, int has_bits, int has_a_amax, int has_b_amax, int has_c_amax,
+                                      int bf16_out)
 {
-  const int dbg = g_pd_dbg_f16x2;
-  static const bool rows_k256 = []() { const char *e = getenv("PD_H2_ROWS_K256"); return !e || e[0] != '0'; }();
-  if ((dbg == 61 || (rows_k256 && dbg == 0)) && mode == 0 && K == 256 && (N % 256) == 0 && M >= 8192) return 2;
-#ifdef PD_PROBES
-  if ((dbg == 90 || (dbg >= 100 && dbg < 132)) && mode == 0 && K == 256 && M >= 4096 && (N % 32) == 0 && N >= 96 && ((N % 128) == 0 || (N % 96) == 0)) return 3;
-#endif
-  if (dbg != 62 && dbg != 3 && dbg != 13 && dbg != 70 && (mode == 1 || mode == 2) && has_bits && K == 256 && (N % 256) == 0 && N >= 512 && M >= 8192 && has_amax && g_rows_relu) return 2;
-  static const bool kpc_env = []() { const char *e = getenv("PD_H2_KPC"); return !e || e[0] != '0'; }();
-  if (((kpc_env && dbg == 0) || dbg == 92 || dbg == 93) && mode == 0 && !has_bits && K >= 512 && (K % KR_KC) == 0 && (N % 256) == 0 && N <= 512 && M >= 8192 && kpc_items_ok(M, N)) return 5;
-#ifdef PD_PROBES
-  static const bool kres_env = []() { const char *e = getenv("PD_H2_KRES"); return e && e[0] == '1'; }();
-  if (((kres_env && dbg == 0) || dbg == 91) && mode == 0 && !has_bits && K >= 512 && (K % KR_KC) == 0 && (N % 256) == 0 && N <= 512 && M >= 8192) return 4;
-#endif
-  const bool wide_ok = (N % 256) == 0 && M >= 1024;
-  const bool by_shape = dbg == 0 || dbg == 61 || dbg == 70 || dbg == 80 || dbg == 62;
-  static const bool wide_deepk = []() { const char *e = getenv("PD_H2_WIDE_DEEPK"); return e && e[0] == '1'; }();
-  const bool wide = has_bits || dbg == 3 || dbg == 13 || (by_shape && wide_ok && (int64_t)((M + 255) / 256) * (N / 256) >= 128 && (N >= 1024 || (K >= 512 && wide_deepk)));
-  return wide ? 1 : 0;
+  const F16x2Plan p = f16x2_plan(M, N, K, lda, ldb, mode, has_bits != 0, has_a_amax != 0, has_b_amax != 0, has_c_amax != 0, bf16_out != 0, g_pd_dbg_f16x2,
+                                 cu_count());
+  return p.refuse ? -1 : (int)p.family;
 }
 
 extern "C" int pd_gemm_tn_f16x2(const float *A, const float *B, const float *bias, float *C, uint32_t *bits, float *colsum, const float *a_amax,
@@ -1301,34 +1303,23 @@ extern "C" int pd_conv3x3_nhwc_f16x2(const float *X, const float *Wk, const floa
   const int64_t M = (int64_t)B * H * W;
   if (M > 0x7fffffffLL - 4096) return pd_set_error(PD_ERR_INVALID_ARG, "pd_conv3x3_nhwc_f16x2: too many pixels");
   hipStream_t st = (hipStream_t)stream_;
+  const int dbg = g_pd_dbg_f16x2;
 #ifdef PD_PROBES
-  // producer / consumer wavefronts (gemm_kpc_f16x2<.., CONV>): opt-in (PD_H2_KPC_CONV=1 / pd_debug_set("f16x2_tile", 92)) — correct, and at
-  // config 2's 2 x 256^2 x 256 slower than the tiled kernel (0.496 vs 0.452 ms: 683 row blocks on 256 CUs are 2.67 rounds of 72 chunks each);
-  // 3 % faster at 2 x 320^2 (0.808 vs 0.831 ms)
-  static const bool kpc_conv = []() { const char *e = getenv("PD_H2_KPC_CONV"); return e && e[0] == '1'; }();
-  if (((kpc_conv && g_pd_dbg_f16x2 == 0) || g_pd_dbg_f16x2 == 92 || g_pd_dbg_f16x2 == 234) && x_amax && w_amax && !y_amax && (Co % 256) == 0 && (Ci % KR_KC) == 0 && ((Ci / KR_KC) & (Ci / KR_KC - 1)) == 0 && M >= 8192 &&
+  // producer / consumer wavefronts (gemm_kpc_f16x2<.., CONV>): opt-in (DBG_KPC_ANY) — correct, and at config 2's 2 x 256^2 x 256 slower than
+  // the tiled kernel (0.496 vs 0.452 ms: 683 row blocks on 256 CUs are 2.67 rounds of 72 chunks each); 3 % faster at 2 x 320^2 (0.808 vs 0.831 ms)
+  if ((dbg == DBG_KPC_ANY || dbg == DBG_KPC_PLANES_STAMPS) && x_amax && w_amax && !y_amax && (Co % 256) == 0 && (Ci % KR_KC) == 0 && ((Ci / KR_KC) & (Ci / KR_KC - 1)) == 0 && M >= 8192 &&
       H < 65536 && W < 65536 && M * Ci * 4 < (1ll << 31) && (int64_t)Co * 9 * Ci * 4 < (1ll << 31)) {
-    static int ncu5 = 0;
-    if (!ncu5) { int dev = 0; (void)hipGetDevice(&dev); if (hipDeviceGetAttribute(&ncu5, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu5 < 8) ncu5 = 256; }
-    const int np = Co / 256, nwork = (int)((M + KR_RB - 1) / KR_RB) * np, G = nwork < ncu5 ? nwork : ncu5;
-    static bool cattr = false;
-    if (!cattr) {
-      (void)hipFuncSetAttribute((const void *)(gemm_kpc_f16x2<true, 0, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)KP_LDS);
-      cattr = true;
-    }
-    if (g_pd_dbg_f16x2 == 234) {                                       // tools: phase stamps (tools/debug/kpc_trace.py conv)
-      (void)hipFuncSetAttribute((const void *)(gemm_kpc_f16x2<true, 16, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)KP_LDS);
-      hipLaunchKernelGGL((gemm_kpc_f16x2<true, 16, false, true>), dim3((unsigned)G), dim3(768), KP_LDS, st, X, Wk, bias, Y, (int)M, 9 * Ci, Ci, 9 * Ci, Co, np, x_amax,
-                         w_amax, H, W);
+    const int np = Co / 256, G = items_grid(cu_count(), M, np);
+    if (dbg == DBG_KPC_PLANES_STAMPS) {                                // tools: phase stamps (tools/debug/kpc_trace.py conv)
+      launch_lds<gemm_kpc_f16x2<true, 16, false, true>>(G, 768, KP_LDS, st, X, Wk, bias, Y, (int)M, 9 * Ci, Ci, 9 * Ci, Co, np, x_amax, w_amax, H, W);
       return pd_check_launch("pd_conv3x3_nhwc_f16x2 (producer / consumer wavefronts, stamps)");
     }
-    hipLaunchKernelGGL((gemm_kpc_f16x2<true, 0, false, true>), dim3((unsigned)G), dim3(768), KP_LDS, st, X, Wk, bias, Y, (int)M, 9 * Ci, Ci, 9 * Ci, Co, np, x_amax,
-                       w_amax, H, W);
+    launch_lds<gemm_kpc_f16x2<true, 0, false, true>>(G, 768, KP_LDS, st, X, Wk, bias, Y, (int)M, 9 * Ci, Ci, 9 * Ci, Co, np, x_amax, w_amax, H, W);
     return pd_check_launch("pd_conv3x3_nhwc_f16x2 (producer / consumer wavefronts)");
   }
 #endif
-  const bool wide = g_pd_dbg_f16x2 == 3 || (g_pd_dbg_f16x2 != 4 && (Co % 256) == 0 && M >= 65536);
-  if (g_pd_dbg_f16x2 == 70 || g_pd_dbg_f16x2 == 21) {               // the guarded step
+  const bool wide = dbg == DBG_WIDE_1 || (dbg != DBG_TILE_1 && (Co % 256) == 0 && M >= 65536);
+  if (dbg == DBG_GUARDED || dbg == DBG_CONV_KORDER) {                 // the guarded step
     if (wide) return launch_f16x2<256, 256, 128, 16, true>(X, Wk, bias, Y, (int)M, Co, 9 * Ci, Ci, 9 * Ci, Co, 0, nullptr, nullptr, x_amax, w_amax, y_amax, st, H, W);
     return launch_f16x2<128, 128, 64, 16, true>(X, Wk, bias, Y, (int)M, Co, 9 * Ci, Ci, 9 * Ci, Co, 0, nullptr, nullptr, x_amax, w_amax, y_amax, st, H, W);
   }

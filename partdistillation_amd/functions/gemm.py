@@ -122,10 +122,9 @@ def gemm_tn_h2(a, b, bias=None, mode=0, bits=None, colsum=None, a_amax=None, b_a
     if not _TIMING["on"]:                                  # the hot path: no label formatting, no context manager
         _lib.check(L.pd_gemm_tn_f16x2(*args))
         return (c, bits) if (mode == 1 and want_bits) else c
-    which = int(L.pd_gemm_tn_f16x2_which(M, N, K, mode, int(bits is not None), int(a_amax is not None and b_amax is not None)))
+    which = int(L.pd_gemm_tn_f16x2_which(M, N, K, a.stride(0), b.stride(0), mode, int(bits is not None), int(a_amax is not None),
+                                         int(b_amax is not None), int(c_amax is not None), 0))
     # (one label per kernel instantiation, as rocprofv3 names them: the per-launch averages of bench.py and of the profile agree)
-    if which in (4, 5) and c_amax is not None:
-        which = 0                                          # (a launch that wants output row maxima takes the tiled kernel)
     label = (f"gemm_rows_f16x2_k256<true, {mode}>" if which == 2 else f"gemm_ra_f16x2_k256<{mode}>" if which == 3
              else "gemm_kres_f16x2<true, 0>" if which == 4 else "gemm_kpc_f16x2<true, 0, false, false>" if which == 5
              else f"gemm_tn_f16x2<{'256, 256, 128, 16' if which == 1 else '128, 128, 64, 16'}, {mode}>")

@@ -345,7 +345,7 @@ def test_gemm_tn_h2_producer_consumer_kernel_matches_fp64_and_the_tiled_kernel(M
         L.pd_debug_set(b"f16x2_tile", 0)
     L.pd_debug_set(b"f16x2_tile", variant)
     try:
-        assert L.pd_gemm_tn_f16x2_which(M, N, K, 0, 0, int(scaled)) == 5
+        assert L.pd_gemm_tn_f16x2_which(M, N, K, K, K, 0, 0, int(scaled), int(scaled), 0, 0) == 5
         got = gemm.gemm_tn_h2(a, w, b, a_amax=aa, b_amax=wa)
         again = gemm.gemm_tn_h2(a, w, b, a_amax=aa, b_amax=wa)
     finally:
@@ -353,6 +353,55 @@ def test_gemm_tn_h2_producer_consumer_kernel_matches_fp64_and_the_tiled_kernel(M
     assert torch.equal(got, again)
     assert ((got.double() - ref).abs() / rown).max().item() < 3e-6
     assert ((got.double() - tiled.double()).abs() / rown).max().item() < 1e-6
+
+
+def test_gemm_tn_h2_launches_the_kernel_its_plan_names():
+    """the launcher runs the kernel family that pd_gemm_tn_f16x2_which reports for the same arguments: the smallest shapes that reach each
+    family, one torch.profiler session (device activity records), one launch per case, nothing timed."""
+    import re
+    from torch.profiler import ProfilerActivity, profile
+    from partdistillation_amd import lib
+    from partdistillation_amd.functions import gemm
+    L = lib.load()
+    family = {0: "gemm_tn_f16x2<128, 128", 1: "gemm_tn_f16x2<256, 256", 2: "gemm_rows_f16x2_k256", 5: "gemm_kpc_f16x2"}
+    # (M, N, K), mode, sign bits, row maxima in, row maxima out, debug value, bf16 out -> the kernel's name starts with
+    cases = [((8192, 256, 256), 0, False, True, False, 0, False, "gemm_rows_f16x2_k256"),
+             ((8192, 512, 256), 1, True, True, False, 0, False, "gemm_rows_f16x2_k256<true, 1"),
+             ((8192, 256, 512), 0, False, False, False, 0, False, "gemm_kpc_f16x2"),
+             ((8192, 256, 512), 0, False, False, True, 0, False, "gemm_tn_f16x2<128, 128"),
+             ((8192, 1024, 512), 0, False, False, False, 0, False, "gemm_tn_f16x2<256, 256"),
+             ((8191, 256, 256), 0, False, False, False, 0, False, "gemm_tn_f16x2<128, 128"),
+             ((8192, 256, 256), 0, False, False, False, 80, False, "gemm_tn_f16x2<128, 128"),
+             ((8192, 256, 256), 0, False, False, False, 0, True, "gemm_tn_f16x2<128, 128")]
+    torch.manual_seed(11)
+    a = {K: torch.randn(8192, K, device="cuda") for K in (256, 512)}
+    w = {(N, K): torch.randn(N, K, device="cuda") * K ** -0.5 for (_, N, K) in {c[0] for c in cases}}
+    aa = {K: gemm.row_amax(v) for K, v in a.items()}
+    wa = {k: gemm.row_amax(v) for k, v in w.items()}
+    cm = torch.zeros(8192, device="cuda")
+    torch.cuda.synchronize()
+    which = []
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        for (M, N, K), mode, bits, amax, c_out, dbg, bf16, _ in cases:
+            x, am = a[K][:M], (aa[K][:M] if amax else None)
+            L.pd_debug_set(b"f16x2_tile", dbg)
+            try:
+                which.append(L.pd_gemm_tn_f16x2_which(M, N, K, K, K, mode, int(bits), int(amax), int(amax), int(c_out), int(bf16)))
+                if bf16:
+                    gemm.gemm_tn_h2_bf16out(x, w[N, K])
+                else:
+                    gemm.gemm_tn_h2(x, w[N, K], mode=mode, want_bits=bits, a_amax=am, b_amax=wa[N, K] if amax else None, c_amax=cm[:M] if c_out else None)
+            finally:
+                L.pd_debug_set(b"f16x2_tile", 0)
+        torch.cuda.synchronize()
+    kernels = sorted((e for e in prof.events() if getattr(e, "device_type", None) is not None and "CUDA" in str(e.device_type)),
+                     key=lambda e: e.time_range.start)
+    names = [re.sub(r"\(anonymous namespace\)::", "", re.sub(r"^void ", "", e.name)) for e in kernels]
+    names = [n for n in names if n.startswith("gemm_")]
+    assert len(names) == len(cases), names
+    for case, wh, name in zip(cases, which, names):
+        assert name.startswith(family[wh]), (case, wh, name)
+        assert name.startswith(case[-1]), (case, wh, name)
 
 
 def test_gemm_tn_h2_relu_bits_and_mask_epilogues():

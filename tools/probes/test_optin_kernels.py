@@ -66,7 +66,7 @@ def test_gemm_tn_h2_resident_accumulators_match_fp64_and_the_tiled_kernel(M, N, 
         L.pd_debug_set(b"f16x2_tile", 0)
     L.pd_debug_set(b"f16x2_tile", variant)
     try:
-        assert variant != 91 or L.pd_gemm_tn_f16x2_which(M, N, K, 0, 0, int(scaled)) == 4
+        assert variant != 91 or L.pd_gemm_tn_f16x2_which(M, N, K, K, K, 0, 0, int(scaled), int(scaled), 0, 0) == 4
         got = gemm.gemm_tn_h2(a, w, b, a_amax=aa, b_amax=wa)
         again = gemm.gemm_tn_h2(a, w, b, a_amax=aa, b_amax=wa)
     finally:
