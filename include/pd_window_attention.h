@@ -1,6 +1,7 @@
 /*
  * pd_window_attention.h — C-ABI of the Swin (shifted-)window attention kernels of libpd_hip.so: window 12 x 12 = 144
- * tokens, head_dim 32, bf16 operands on the matrix cores, fp32 scores / softmax.
+ * tokens (Swin-B / Swin-L at 384, *_w12) and window 7 x 7 = 49 tokens (Swin-T / Swin-S, *_w7, at the end of this comment), head_dim 32,
+ * bf16 operands on the matrix cores, fp32 scores / softmax.
  *
  * Replaces, per Swin block, the body of the reference's WindowAttention.forward
  *   modeling/backbone/swin.py:135-175
@@ -28,6 +29,19 @@
  *   win_flags : uint8 [nW], nonzero = this window has more than one region (others skip the mask arithmetic)
  *   lse       : fp32 [B_, heads, 144], BASE-2 log-sum-exp of the scores (forward output, backward input)
  * `stream` = hipStream_t.  Returns 0 or PD_ERR_* (pd_msda.h); message via pd_last_error().
+ *
+ * Window 7 (pd_window_attn_*_w7): the same math and conventions with 49 tokens and a [169, heads] table:
+ *   index(q, key) = A(q) - A(key) + 84,  A(t) = t + 6 * (t / 7)
+ * (A(t) = 13 * row + col of token t and 84 = 6 * 13 + 6: the reference's relative_position_index for a 7 x 7 window).
+ *   qkv, dqkv : bf16 [B_, 49, 3*C], C = heads*32; q of head h at column h*32, k at C + h*32, v at 2C + h*32
+ *   out, d_out: bf16 [B_, 49, C]
+ *   table     : fp32 [169, heads]; dtable: fp32 [169, heads], ACCUMULATED into (atomics) — the caller zero-fills
+ *   region    : uint8 [nW, 49] or NULL (no alignment requirement); win_flags: uint8 [nW]
+ *   lse       : fp32 [B_, heads, 49], base-2
+ * Padding rule: 49 is not a multiple of the 16-row MFMA tile, so the on-chip tiles have 64 rows, 15 of them padding.  A padded KEY has
+ * weight exactly zero (score -inf, never the mask's -100); a padded QUERY row is never written to out, lse or dqkv and contributes
+ * nothing to dK, dV or dtable; the padded rows of the on-chip tiles hold zeros (0 * stale NaN would poison a real row through the MFMA).
+ * Nothing is read or written outside the [B_, 49, ...] tensors.  No MX-fp8 operand copies at this window size.
  */
 #ifndef PD_WINDOW_ATTENTION_H
 #define PD_WINDOW_ATTENTION_H
@@ -48,6 +62,15 @@ int pd_window_attn_fwd_w12(const void *qkv, const float *table, const uint8_t *r
 int pd_window_attn_bwd_w12(const void *qkv, const float *table, const uint8_t *region, const uint8_t *win_flags,
                            const void *out, const void *d_out, const float *lse, void *dqkv, float *dtable, int B_, int nW,
                            int heads, float scale, void *dqkv_q, void *dqkv_s, int q_format, void *stream);
+
+/* window 7 x 7 (layouts and the padding rule: the end of the comment above) */
+int pd_window_attn_fwd_w7(const void *qkv, const float *table, const uint8_t *region, const uint8_t *win_flags, void *out,
+                          float *lse, int B_, int nW, int heads, float scale, void *stream);
+
+/* dqkv is written completely; dtable is accumulated into */
+int pd_window_attn_bwd_w7(const void *qkv, const float *table, const uint8_t *region, const uint8_t *win_flags,
+                          const void *out, const void *d_out, const float *lse, void *dqkv, float *dtable, int B_, int nW,
+                          int heads, float scale, void *stream);
 
 #ifdef __cplusplus
 }

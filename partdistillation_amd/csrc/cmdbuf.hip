@@ -209,7 +209,9 @@ const Entry kTable[] = {
   PD_E(pd_wgrad_bf16),
   PD_E(pd_wgrad_bf16_seq),
   PD_E(pd_window_attn_bwd_w12),
+  PD_E(pd_window_attn_bwd_w7),
   PD_E(pd_window_attn_fwd_w12),
+  PD_E(pd_window_attn_fwd_w7),
 };
 constexpr int kCount = (int)(sizeof(kTable) / sizeof(kTable[0]));
 }  // namespace

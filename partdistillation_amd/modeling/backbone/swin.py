@@ -175,7 +175,7 @@ class SwinTransformerBlock(nn.Module):
         idx, inv, n_win, any_pad = gather
         xw = _WindowGather.apply(x, idx, inv, any_pad).reshape(B * n_win, ws * ws, C)   # padded slots read a zero row
         shifted = self.shift_size > 0
-        regions = wattn.shifted_window_regions(H, W, self.shift_size, x.device) if shifted and ws == wattn.WINDOW else None
+        regions = wattn.shifted_window_regions(H, W, self.shift_size, x.device, window=ws) if shifted and ws in wattn.WINDOWS else None
         aw = self.attn(xw, mask=mask_matrix if shifted else None, regions=regions, n_windows=n_win)
         x = _WindowScatter.apply(aw.reshape(B, n_win * ws * ws, C), idx, inv, any_pad)
         x = shortcut + self.drop_path(x)
@@ -296,7 +296,7 @@ def shifted_window_mask(H, W, ws, shift, device):
             for wsl in (slice(0, -ws), slice(-ws, -shift), slice(-shift, None)):
                 img[:, hs, wsl, :] = cnt
                 cnt += 1
-        mw = window_partition(img, ws).view(-1, ws * ws)
+        mw = window_partition(img, ws).reshape(-1, ws * ws)               # (one row of windows comes back as a strided view: .view fails on it)
         am = mw.unsqueeze(1) - mw.unsqueeze(2)
         _MASK_CACHE[key] = am.masked_fill(am != 0, -100.0).masked_fill(am == 0, 0.0).to(device)
     return _MASK_CACHE[key]
