@@ -65,7 +65,17 @@ int pd_msda_forward_amax(const void *value, const int64_t *spatial_shapes, const
                          const void *attn_weight, void *output, float *row_amax, int batch, int spatial_size, int num_heads, int channels,
                          int num_levels, int num_query, int num_point, int im2col_step, int dtype, void *stream);
 
-/* replaces MSDA.ms_deform_attn_backward (vision.cpp:21, ms_deform_attn_cuda.cu:89-159) */
+/* replaces MSDA.ms_deform_attn_backward (vision.cpp:21, ms_deform_attn_cuda.cu:89-159).
+ * attn_weight is ANY tensor, as in the reference: nothing has to be normalised, positive or bounded.  For the self-attention
+ * geometry (fp32, 32 channels, 4 points, num_query == spatial_size) grad_value is accumulated in int32 fixed-point LDS windows,
+ * which is exact to 2^-23 of a tile's max |grad_output| per add ONLY while every |attn_weight| <= 1 and the |attn_weight| of all
+ * samples of the queries one tile owns (the unit square is cut into G x G tiles, G = min(16, ceil(largest level dimension / 16)))
+ * sum to at most 511 — a softmax over a head's 12 samples gives 336 at a 4:2:1 pyramid.  The kernels test this per (image, tile,
+ * head), and a tile outside it — a weight above 1, unnormalised weights, a NaN weight, a non-finite grad_output (NaN included) —
+ * is accumulated with plain fp32 global atomics instead: slower, and correct for every input; a non-finite grad_output reaches
+ * exactly the cells its query samples.  The fused form below, whose weights are a softmax by construction, applies the rule as
+ * a count: a tile that owns 512 queries or more takes the global atomics (e.g. three 16 x 16 levels: one tile of 768 queries;
+ * a 4:2:1 pyramid stays below it up to a largest level of 256 x 256, 336 queries per tile). */
 int pd_msda_backward(const void *value, const int64_t *spatial_shapes, const int64_t *level_start_index,
                      const void *sampling_loc, const void *attn_weight, const void *grad_output,
                      void *grad_value, void *grad_sampling_loc, void *grad_attn_weight,
@@ -113,7 +123,10 @@ int pd_abi_version(void);
  * sample points that leave the 5-cell windows and publishes {missed, looked-at} to host-mapped memory when it finishes; a launch
  * takes the 9-cell kernel when the most recent results that have arrived show more than 2 % misses (pd_debug_set("msda_gate_pct",
  * per_mille); measured break-even: 0.9 % -> 0.28 vs 0.39 ms, 3.9 % -> 0.63 vs 0.40 ms per launch at BASELINE config-2 geometry).  out3 <- {missed, looked-at} of the most recent launch whose result has arrived, and the
- * variant the most recent launch took (2 = 9-cell halo, 3 = 5-cell halo).  Reads host memory only, never synchronises. */
+ * variant the most recent launch took (2 = 9-cell halo, 3 = 5-cell halo).  Reads host memory only, never synchronises.
+ * In the 5-cell kernel a tile that uses no window (non-finite grad_output; 512 or more queries in the fused form) is left out of
+ * both counts, and a launch made of such tiles only publishes nothing: the earlier results keep standing.  The 9-cell kernel
+ * counts against the 5-cell windows geometrically, whatever it does with the corners. */
 int pd_msda_backward_last_gate(unsigned *out3);
 
 #ifdef __cplusplus

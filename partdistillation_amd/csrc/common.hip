@@ -101,3 +101,12 @@ extern "C" int pd_debug_set(const char *key, int value)
   if (!strcmp(key, "msda_force_generic")) { g_pd_dbg_force_generic = value; return PD_OK; }
   return pd_set_error(PD_ERR_INVALID_ARG, "pd_debug_set: unknown key %s", key);
 }
+
+// the value in force of the knobs that tests change and have to put back (the MSDA backward's variant and gate threshold)
+extern "C" int pd_debug_get(const char *key, int *value)
+{
+  if (!key || !value) return PD_ERR_INVALID_ARG;
+  if (!strcmp(key, "msda_bwd_variant")) { *value = g_pd_dbg_bwd_variant; return PD_OK; }
+  if (!strcmp(key, "msda_gate_pct")) { *value = g_pd_dbg_msda_gate_pct; return PD_OK; }
+  return pd_set_error(PD_ERR_INVALID_ARG, "pd_debug_get: unknown key %s", key);
+}

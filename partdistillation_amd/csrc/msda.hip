@@ -496,21 +496,38 @@ __global__ __launch_bounds__(256) void msda_bwd_d32(const float *__restrict__ va
 // source levels) and accumulates their contributions to the destination level
 // into an LDS window (tile + HALO cells each side, <= WIN x WIN cells x 32
 // channels) as int32 fixed point with a per-(workgroup, channel) power-of-two
-// scale 2^e, e = 22 - exponent(max |grad_out| over the tile's queries): every
-// contribution is |grad_out*attn*w| <= max < 2^22 after scaling and the bilinear
-// x attention weights of one tile's queries sum to < 2^9 per cell, so the int32
-// sum cannot overflow; quantisation error is <= 2^-23 of that max per add (the
-// same order as the fp32 re-association noise of the reference's atomics) and
-// the accumulation is order-independent.  The window is flushed once with
-// full-128-byte-line fp32 atomics.  Samples that land outside the window (large
-// learned offsets) take the direct global atomic, so the result never depends on
-// G, HALO or WIN — the window is only a cache.
+// scale 2^e, e = 22 - exponent(max |grad_out| over the tile's queries).  The
+// int32 sum stays below 2^31 under a PRECONDITION on the attention weights that
+// the operator's ABI does not promise (it takes any attn_weight): every |attn| <= 1,
+// so that a contribution |grad_out*attn*w| is < 2^22 after scaling, and the
+// |attn| of the samples one tile sends to the level sum to < 2^9 (bilinear
+// weights are <= 1, so this bounds what one cell can receive).  Softmax weights
+// meet it whenever a tile owns fewer than 512 queries (336 at the standard
+// pyramid); weights above 1, unnormalised weights (1 on all 12 samples: 1344
+// per tile) and three equal-sized levels (768 queries per tile) do not, and
+// a sum that wraps is wrong by ~2^10 of the tile's max |grad_out|.  So THIS
+// kernel's pre-pass, which finds the scale, also reads the tile's attention
+// rows, and a workgroup outside the precondition (max |a| > 1, sum |a| >
+// kFixedSumMax, or a NaN weight) uses no window at all: it takes the direct
+// global atomics below, which are correct for every input
+// (tests/test_msda_windows_gpu.py).  (The owner kernels further down test the
+// same precondition in other places: see there.)  Inside it
+// the quantisation error is <= 2^-23 of that max per add (the same order as the
+// fp32 re-association noise of the reference's atomics) and the accumulation is
+// order-independent.  The window is flushed once with full-128-byte-line fp32
+// atomics.  Samples that land outside the window (large learned offsets) take
+// the direct global atomic, so the result never depends on G, HALO or WIN — the
+// window is only a cache.
 // G is derived in-kernel from the device-resident shapes (the ABI carries no host
 // copy): G = ceil(max level dim / TILE); the host launches GMAX^2 tiles and the
 // surplus blocks exit at once.
 constexpr int kTile = 16, kHalo = 4, kWin = kTile + 2 * kHalo, kGmax = 16;
+// the bound on sum |cw a| per cell under which a workgroup may use its fixed-point window (2^9, less room for the roundings of
+// the adds and of the sum itself); the fused kernels, whose weights are a softmax, compare the tile's query count with 512
+constexpr float kFixedSumMax = 511.f;
 
 __device__ __forceinline__ int lds_slot(int cell, int ch) { return cell * 32 + ((ch + (cell & 3)) & 31); }
+__device__ __forceinline__ int abs_bits(float x) { return __float_as_int(x) & 0x7fffffff; }
 
 template <int P_, int ABL>
 __global__ __launch_bounds__(1024) void msda_bwd_tiled_d32(const float *__restrict__ value, const int64_t *__restrict__ shapes,
@@ -538,9 +555,12 @@ __global__ __launch_bounds__(1024) void msda_bwd_tiled_d32(const float *__restri
   const int wh = min(min(H, (ty + 1) * H / G + kHalo) - wy0, kWin), ww = min(min(W, (tx + 1) * W / G + kHalo) - wx0, kWin);
   const int cells = max(wh, 0) * max(ww, 0);
   int *chmax = win + kWin * kWin * 32;
+  __shared__ float s_asum;                      // sum |attn| of the tile's samples at this level, and whether one exceeds 1
+  __shared__ int s_abig;
   const int NT = blockDim.x, NG = NT >> 3;      // threads, 8-lane query groups per workgroup
   for (int i = threadIdx.x; i < cells * 32; i += NT) win[i] = 0;
   if (threadIdx.x < 32) chmax[threadIdx.x] = 0;
+  if (threadIdx.x == 0) { s_asum = 0.f; s_abig = 0; }
   __syncthreads();
 
   const int sub = threadIdx.x & 7, grp = threadIdx.x >> 3;
@@ -549,9 +569,11 @@ __global__ __launch_bounds__(1024) void msda_bwd_tiled_d32(const float *__restri
   const int64_t voff = ((int64_t)b * S + lvl_start[l]) * stride_w + m * 32 + sub * 4;
   const float *vbase = value + voff;
   float *gbase = grad_value + voff;
-  // ---- pre-pass: per-channel max |grad_out| over this tile's queries -> fixed-point scale
+  // ---- pre-pass: per-channel max |grad_out| over this tile's queries -> fixed-point scale; and the attention weights the
+  // tile sends to this level (the precondition of the fixed-point window, see above)
   {
-    float mx[4] = {0.f, 0.f, 0.f, 0.f};
+    int mx[4] = {0, 0, 0, 0};       // |x| as its bit pattern: orders like the float, and a NaN (which fmaxf would drop) is the largest
+    float asum = 0.f, amax = 0.f;
     for (int j = 0; j < L; ++j) {
       const int Hj = (int)shapes[2 * j], Wj = (int)shapes[2 * j + 1];
       const int ry0 = ty * Hj / G, ry1 = (ty + 1) * Hj / G, rx0 = tx * Wj / G, rx1 = (tx + 1) * Wj / G;
@@ -560,17 +582,30 @@ __global__ __launch_bounds__(1024) void msda_bwd_tiled_d32(const float *__restri
       for (int i = grp; i < nq; i += NG) {
         const int q = qbase + (ry0 + i / rw) * Wj + rx0 + i % rw;
         const float4 go = *reinterpret_cast<const float4 *>(grad_out + (((int64_t)b * S + q) * M + m) * 32 + sub * 4);
-        mx[0] = fmaxf(mx[0], fabsf(go.x)); mx[1] = fmaxf(mx[1], fabsf(go.y));
-        mx[2] = fmaxf(mx[2], fabsf(go.z)); mx[3] = fmaxf(mx[3], fabsf(go.w));
+        mx[0] = max(mx[0], abs_bits(go.x)); mx[1] = max(mx[1], abs_bits(go.y));
+        mx[2] = max(mx[2], abs_bits(go.z)); mx[3] = max(mx[3], abs_bits(go.w));
+        if (sub == 0) {
+          const float4 a4 = *reinterpret_cast<const float4 *>(attn + (((int64_t)b * S + q) * M + m) * LP + l * P_);
+          const float s01 = fabsf(a4.x) + fabsf(a4.y), s23 = fabsf(a4.z) + fabsf(a4.w);
+          asum += s01 + s23;                    // (a NaN weight makes the sum NaN: caught by the comparison below)
+          amax = fmaxf(amax, fmaxf(fmaxf(fabsf(a4.x), fabsf(a4.y)), fmaxf(fabsf(a4.z), fabsf(a4.w))));
+        }
       }
     }
 #pragma unroll
-    for (int c = 0; c < 4; ++c)   // non-negative floats order like their bit patterns; NaN/inf handled below
-      atomicMax(&chmax[sub * 4 + c], __float_as_int(mx[c]));
+    for (int c = 0; c < 4; ++c)   // NaN / inf handled below
+      atomicMax(&chmax[sub * 4 + c], mx[c]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { asum += __shfl_xor(asum, o, 64); amax = fmaxf(amax, __shfl_xor(amax, o, 64)); }
+    if ((threadIdx.x & 63) == 0) {
+      atomicAdd(&s_asum, asum);
+      if (amax > 1.f) s_abig = 1;
+    }
   }
   __syncthreads();
   float qscale[4], dscale[4];
-  bool fixed_ok = true;
+  // outside the precondition (a weight above 1, or weights that sum to kFixedSumMax or more): no window, plain global atomics
+  bool fixed_ok = s_abig == 0 && s_asum <= kFixedSumMax;
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     const float mxc = __int_as_float(chmax[sub * 4 + c]);
@@ -695,8 +730,17 @@ __global__ __launch_bounds__(1024) void msda_bwd_tiled_d32(const float *__restri
 //     offset) out of the loop into a rolled epilogue that re-reads the point, so it costs the loop no registers;
 //   * uses 24-bit multiplies (full rate; v_mul_lo_u32 is quarter rate) for pixel / element indices — the host admits the
 //     kernel only when they fit.
-// Same fixed-point scheme and guarantees as above (order-independent, cannot overflow, result independent of tile / halo
-// sizes).  Levels whose window does not fit the LDS budget (non-pyramid shapes) get no window: direct atomics.
+// Same fixed-point scheme, precondition and guarantees as above (order-independent, result independent of tile / halo sizes).
+// Here the precondition matters twice: the one-FMA rounding yields 0x4B400000 + integer only while |weight * grad_out * scale|
+// < 2^22, i.e. |attn| <= 1 (a single sample with attn = 3 on a pixel centre leaves the binade and the flush's correction no
+// longer cancels), and the cell sums must stay below 2^31.  It is checked per workgroup.  The fused form, whose weights are a
+// softmax, clears fixed_ok in the pre-pass when the tile owns 512 queries or more: everything then goes through direct global
+// atomics.  The operator form tests max |attn| <= 1 and sum |attn| <= kFixedSumMax over ALL the tile's samples (conservative: a
+// cell belongs to one level).  Its halo-5 kernel sums the |attn| that its main pass loads anyway, and a workgroup that finds
+// itself outside drops its windows instead of flushing them and adds the corners they had cached with global atomics in a
+// second walk over its units.  Its halo-9 kernel (HALF, below), with no register to spare in the main pass, reads the tile's
+// attention rows in the pre-pass and clears fixed_ok like the fused form.
+// Levels whose window does not fit the LDS budget (non-pyramid shapes) get no window: direct atomics.
 // 0.378 -> 0.233 ms per launch at config 2 (tools/bench_msda.py, default spread).
 constexpr int kHalo4 = 5, kWin4 = kTile + 2 * kHalo4, kOwnCells4 = 1200;
 // HALF (round 3): the same kernel with the 32 channels of a head split over TWO workgroups.  A cell is then 17 words instead of
@@ -706,6 +750,12 @@ constexpr int kHalo4 = 5, kWin4 = kTile + 2 * kHalo4, kOwnCells4 = 1200;
 // instead of 0.23 — and stays there up to offsets of ~4 cells sigma, where the halo-5 kernel spends 2 ms in its global-atomic
 // fallback (40 % of the corners miss its windows).  pd_msda_backward picks per launch from a sampled miss count (below).
 constexpr int kHalo4H = 9, kWin4H = kTile + 2 * kHalo4H, kOwnCells4H = 2330;
+
+template <int CTRL>
+__device__ __forceinline__ unsigned dpp_addu(unsigned x)
+{
+  return x + (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xF, 0xF, true);
+}
 
 __device__ __forceinline__ float group4_sum(float x)
 {
@@ -787,9 +837,12 @@ __global__ __launch_bounds__(1024) void msda_bwd_owner4_d32(const float *__restr
   __shared__ LvlP lvp[L];
   struct QLv { int rw, w, base, first, n, pad0, pad1, pad2; };   // the tile's queries of source level j: rows of rw pixels in a map of width w, from query `base`; `first` = queries of the levels before
   __shared__ QLv lq[L];
-  __shared__ int s_used, s_fixed_ok, s_miss;
+  __shared__ int s_used, s_fixed_ok, s_miss, s_abad;
+  __shared__ unsigned s_asum;                                // operator form: 4 x the sum |attn| over the tile's samples in 1 / 256ths, rounded up (s_abad: a weight above 1, or a NaN)
   if (threadIdx.x == 0) {
     s_miss = 0;
+    s_abad = 0;
+    s_asum = 0u;
     int used = 0;
 #pragma unroll
     for (int j = 0; j < L; ++j) {
@@ -824,11 +877,6 @@ __global__ __launch_bounds__(1024) void msda_bwd_owner4_d32(const float *__restr
   const int NT = blockDim.x;
   if (threadIdx.x < 32) chmax[threadIdx.x] = 0;
   __syncthreads();
-  {
-    int4 *w4 = reinterpret_cast<int4 *>(win);
-    const int n4 = (s_used * CW + 3) >> 2;
-    for (int i = threadIdx.x; i < n4; i += NT) w4[i] = make_int4(0, 0, 0, 0);
-  }
   const int stride_w = M * 32;
   // the tile's queries: source level j contributes the pixels [ry0, ry1) x [rx0, rx1)
   // (level constants of a query in LDS, not in arrays: of `j == 0 ? rw[0] : j == 1 ? rw[1] : rw[2]` the compiler made rw[j] on a STACK array — the
@@ -841,20 +889,75 @@ __global__ __launch_bounds__(1024) void msda_bwd_owner4_d32(const float *__restr
     const int il = i - t.first, y = il / t.rw, x = il - y * t.rw;
     return t.base + y * t.w + x;
   };
-  // ---- pre-pass: per-channel max |grad_out| over the tile's queries (8 lanes x float4 per query row) -> fixed-point scale
+  // ---- pre-pass: per-channel max |grad_out| over the tile's queries (8 lanes x float4 per query row) -> fixed-point scale.
+  // Three rows (what a lane group has at 384 queries) are requested together, and the windows are cleared while they arrive.
+  // Where the operator form tests its precondition on the attention weights (every |a| <= 1, sum |a| <= kFixedSumMax over the tile):
+  // the halo-5 kernel in its main pass, on the weights that pass loads anyway, with a second walk for a tile found outside; the halo-9
+  // kernel, whose main pass has no register left for that, here — lanes 0 .. 2 of a query's 8-lane group take a level's four weights
+  // each, at the address the group has formed for the grad_out row — and a tile outside uses no window from the start.
+  constexpr bool PRE_CHECK = !FUSED && HALF, POST_CHECK = !FUSED && !HALF;
   {
     const int sub8 = threadIdx.x & 7, grp8 = threadIdx.x >> 3, NG8 = NT >> 3;
-    float mx[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int i = grp8; i < nq_all; i += NG8) {
-      const int q = query_of(i);
-      const float4 go = *reinterpret_cast<const float4 *>(grad_out + (((int64_t)b * S + q) * M + m) * 32 + sub8 * 4);
-      mx[0] = fmaxf(mx[0], fabsf(go.x)); mx[1] = fmaxf(mx[1], fabsf(go.y));
-      mx[2] = fmaxf(mx[2], fabsf(go.z)); mx[3] = fmaxf(mx[3], fabsf(go.w));
-    }
+    constexpr int U = 3;
+    int mx[4] = {0, 0, 0, 0};       // |x| as its bit pattern: orders like the float, and a NaN (which fmaxf would drop) is the largest
+    float asum = 0.f, amax = 0.f;
+    float4 go[U], aw[U];
+    auto request = [&](int i0) {
 #pragma unroll
-    for (int c = 0; c < 4; ++c) atomicMax(&chmax[sub8 * 4 + c], __float_as_int(mx[c]));   // non-negative floats order like their bits
+      for (int u = 0; u < U; ++u) {
+        const int i = i0 + u * NG8;
+        go[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+        aw[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (i < nq_all) {
+          const int64_t qm = ((int64_t)b * S + query_of(i)) * M + m;
+          go[u] = *reinterpret_cast<const float4 *>(grad_out + qm * 32 + sub8 * 4);
+          if constexpr (PRE_CHECK) {
+            if (sub8 < L) aw[u] = *reinterpret_cast<const float4 *>(attn + qm * LP + sub8 * P);
+          }
+        }
+      }
+    };
+    auto take = [&]() {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        mx[0] = max(mx[0], abs_bits(go[u].x)); mx[1] = max(mx[1], abs_bits(go[u].y));
+        mx[2] = max(mx[2], abs_bits(go[u].z)); mx[3] = max(mx[3], abs_bits(go[u].w));
+        if constexpr (PRE_CHECK) {
+          const float s01 = fabsf(aw[u].x) + fabsf(aw[u].y), s23 = fabsf(aw[u].z) + fabsf(aw[u].w);
+          asum += s01 + s23;                                // (a NaN weight makes the sum NaN: counted as too large below)
+          amax = fmaxf(amax, fmaxf(fmaxf(fabsf(aw[u].x), fabsf(aw[u].y)), fmaxf(fabsf(aw[u].z), fabsf(aw[u].w))));
+        }
+      }
+    };
+    request(grp8);
+    {
+      int4 *w4 = reinterpret_cast<int4 *>(win);
+      const int nw = s_used * CW, n4 = nw >> 2;             // (whole int4s only: the words behind the last cell are chmax, which other waves are already writing)
+      for (int i = threadIdx.x; i < n4; i += NT) w4[i] = make_int4(0, 0, 0, 0);
+      if ((int)threadIdx.x < (nw & 3)) win[4 * n4 + threadIdx.x] = 0;
+    }
+    take();
+    for (int i0 = grp8 + U * NG8; i0 < nq_all; i0 += U * NG8) { request(i0); take(); }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) atomicMax(&chmax[sub8 * 4 + c], mx[c]);
+    if constexpr (PRE_CHECK) {
+      if (amax > 1.f) s_abad = 1;                           // (no reduction needed: any lane that saw one says so)
+      asum = dpp_add<0x140>(group8_sum(asum));              // the wave's four rows of 16 lanes (row_mirror after the 8-lane sums) ...
+      const float w = (__int_as_float(__builtin_amdgcn_readlane(__float_as_int(asum), 0)) + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(asum), 16))) +
+                      (__int_as_float(__builtin_amdgcn_readlane(__float_as_int(asum), 32)) + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(asum), 48)));
+      // ... and ONE LDS add per wave, in 1 / 256ths rounded up (a NaN or a huge sum counts as 10^6)
+      if ((threadIdx.x & 63) == 0) atomicAdd(&s_asum, (unsigned)((w <= 1.0e6f ? w : 1.0e6f) * 256.f + 0.999f));
+    }
   }
   __syncthreads();
+  if (threadIdx.x == 0) {
+    // softmax weights (fused form): every a <= 1 and a query's weights sum to 1, so the tile's query count bounds the sum
+    if (FUSED && nq_all >= 512) s_fixed_ok = 0;
+    if (PRE_CHECK && (s_abad != 0 || s_asum > (unsigned)(256.f * kFixedSumMax))) s_fixed_ok = 0;
+    // the halo-5 operator kernel keeps its sum in 19 spare bits of a lane's miss counter (below): a tile with 511 units or more per
+    // lane — 43 000 queries; any normalised weights put it outside the precondition anyway — uses no window
+    if (POST_CHECK && nq_all * L >= 511 * (NT >> 2)) s_fixed_ok = 0;
+  }
   if (threadIdx.x < 32) {
     const float mxc = __int_as_float(chmax[threadIdx.x]);
     int ex;
@@ -912,6 +1015,15 @@ __global__ __launch_bounds__(1024) void msda_bwd_owner4_d32(const float *__restr
       const float4 *lp4 = reinterpret_cast<const float4 *>(loc + (qm * LP + l * P) * 2);
       l01 = lp4[0]; l23 = lp4[1];
       a4 = *reinterpret_cast<const float4 *>(attn + qm * LP + l * P);
+      if constexpr (POST_CHECK) {
+        const float s4 = (fabsf(a4.x) + fabsf(a4.y)) + (fabsf(a4.z) + fabsf(a4.w));
+        const bool badw = !(fabsf(a4.x) <= 1.f) || !(fabsf(a4.y) <= 1.f) || !(fabsf(a4.z) <= 1.f) || !(fabsf(a4.w) <= 1.f);   // above 1, or NaN
+        // (no register of its own in this loop: 1 / 256ths, rounded up, in bits 12 .. 30 above the 12 bits nmiss needs; bit 31 = a
+        // weight above 1 or a NaN.  A unit adds at most 4 misses and 1025 to the sum, and a tile that uses its windows has at most
+        // 510 units per lane (the pre-pass sees to it): 2040 < 2^12 and 522 750 < 2^19, so no field reaches the next)
+        nmiss += (unsigned)(fminf(s4, 4.f) * 256.f + 0.999f) << 12;
+        if (badw) nmiss |= 0x80000000u;
+      }
     }
     const float locs[8] = {l01.x, l01.y, l01.z, l01.w, l23.x, l23.y, l23.z, l23.w};
     const float aw[4] = {a4.x, a4.y, a4.z, a4.w};
@@ -1060,12 +1172,63 @@ __global__ __launch_bounds__(1024) void msda_bwd_owner4_d32(const float *__restr
       }
     }
   }
+  if constexpr (POST_CHECK) {
+    // the tile's sum |attn| (all four lanes of a unit added it: 4 x), one LDS add per wave
+    unsigned afx = (nmiss >> 12) & 0x7FFFFu;
+    if (nmiss >> 31) s_abad = 1;
+    nmiss &= 0xFFFu;
+    afx = dpp_addu<0x128>(dpp_addu<0x124>(dpp_addu<0x4E>(dpp_addu<0xB1>(afx))));      // quads, then two rotations inside a row of 16
+    afx = (unsigned)(__builtin_amdgcn_readlane((int)afx, 0) + __builtin_amdgcn_readlane((int)afx, 16)) +
+          (unsigned)(__builtin_amdgcn_readlane((int)afx, 32) + __builtin_amdgcn_readlane((int)afx, 48));
+    if ((threadIdx.x & 63) == 0) atomicAdd(&s_asum, afx);
+  }
   if (cnt) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) nmiss += __shfl_xor(nmiss, o, 64);
     if ((threadIdx.x & 63) == 0 && nmiss) atomicAdd(&s_miss, (int)nmiss);
   }
   __syncthreads();
+  // The halo-5 operator kernel's precondition, known only now.  Outside it the windows hold wrapped or mis-rounded sums: they are
+  // dropped, and the corners they cached are added again with global atomics.
+  bool redo = false;
+  if constexpr (POST_CHECK) {
+    redo = fixed_ok && (s_abad != 0 || s_asum > (unsigned)(4.f * 256.f * kFixedSumMax));
+    if (redo) {
+#pragma unroll 1
+      for (int u = grp; u < nunits; u += NG) {
+        const int qi = u / L, l = u - qi * L;
+        const int64_t qm = ((int64_t)b * S + query_of(qi)) * M + m;
+        const LvlP lv = lvp[l];
+        const int H = lv.H, W = lv.W;
+        const float4 g0 = *reinterpret_cast<const float4 *>(grad_out + qm * 32 + sub * 8), g1 = *reinterpret_cast<const float4 *>(grad_out + qm * 32 + sub * 8 + 4);
+        const float gs[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
+        float *gbase = grad_value + ((int64_t)b * S + lv.ls) * stride_w + m * 32 + sub * 8;
+#pragma unroll 1
+        for (int p = 0; p < P; ++p) {
+          const float2 xy = *reinterpret_cast<const float2 *>(loc + (qm * LP + l * P + p) * 2);
+          const float a = attn[qm * LP + l * P + p];
+          const float h_im = xy.y * H - 0.5f, w_im = xy.x * W - 0.5f;
+          const bool in_range = h_im > -1 && w_im > -1 && h_im < H && w_im < W;
+          int off[4]; bool ok[4]; float cw[4], lh, lw, hh, hw;
+          corner_setup<float>(h_im, w_im, H, W, stride_w, in_range, off, ok, cw, lh, lw, hh, hw);
+          const int cy0 = (in_range ? (int)floorf(h_im) : 0) - lv.wy0, cx0 = (in_range ? (int)floorf(w_im) : 0) - lv.wx0;
+#pragma unroll 1
+          for (int k = 0; k < 4; ++k) {
+            const int cy = cy0 + (k >> 1), cx = cx0 + (k & 1);
+            const bool cached = (unsigned)cy < (unsigned)lv.wh && (unsigned)cx < (unsigned)lv.ww;
+            const int o = k == 0 ? off[0] : k == 1 ? off[1] : k == 2 ? off[2] : off[3];
+            const float w_ = k == 0 ? cw[0] : k == 1 ? cw[1] : k == 2 ? cw[2] : cw[3];
+            const bool okk = k == 0 ? ok[0] : k == 1 ? ok[1] : k == 2 ? ok[2] : ok[3];
+            const float sc = w_ * a;
+            if (!okk || !cached || sc == 0.f) continue;     // exactly what the first walk put into a window
+            float *g = gbase + o;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) unsafeAtomicAdd(g + c, sc * gs[c]);
+          }
+        }
+      }
+    }
+  }
   if constexpr (FUSED && !(ABL & 32)) {
     // closing pass of the softmax backward: d logit_j = a_j g_j - a_j sum_i a_i g_i.  The main pass left a_j g_j in d_oa and every
     // (query, level) unit's partial sum in scratch (plain stores of this workgroup, ordered by the barrier above; summed here in level
@@ -1106,7 +1269,7 @@ __global__ __launch_bounds__(1024) void msda_bwd_owner4_d32(const float *__restr
   for (int l = 0; l < L; ++l) {
     const LvlP lv = lvp[l];
     float *gl = grad_value + ((int64_t)b * S + lv.ls) * stride_w + m * 32;
-    const int cells = lv.wh * lv.ww;
+    const int cells = redo ? 0 : lv.wh * lv.ww;
     constexpr int NCH = HALF ? 16 : 32;                     // channels a cell holds; lane = channel
     for (int i = threadIdx.x; i < cells * NCH; i += NT) {
       const int cellw = i / NCH, cl = i % NCH, ch = half * 16 + cl;
@@ -1124,7 +1287,10 @@ __global__ __launch_bounds__(1024) void msda_bwd_owner4_d32(const float *__restr
     // missed a straggler would only shade a later launch's choice of window size.  A __threadfence() here made every workgroup wait
     // for the write-back of the lines it had just written, with its CU idle (one workgroup per CU): 6 us per launch in the operator
     // kernel, 19 us in the fused one.
-    if (half == 0) {
+    // (a halo-5 tile that bypassed its windows — non-finite grad_out, 512 or more queries in the fused form — sees every corner as
+    // uncached: it says nothing about the halo and is left out of both counts; a launch of such tiles only publishes {0, 0} = nothing.
+    // The halo-9 kernel counts against the halo-5 window geometrically whatever it does with the corners)
+    if (half == 0 && (HALF || s_fixed_ok != 0)) {
       (void)__hip_atomic_fetch_add(cnt, (unsigned)s_miss, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       (void)__hip_atomic_fetch_add(cnt + 1, (unsigned)(nq_all * LP), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }

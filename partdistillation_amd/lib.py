@@ -239,6 +239,7 @@ SIGNATURES = {
     "pd_last_error": (ctypes.c_char_p, []),
     "pd_abi_version": (_c_int, []),
     "pd_debug_set": (_c_int, [ctypes.c_char_p, _c_int]),
+    "pd_debug_get": (_c_int, [ctypes.c_char_p, _c_vp]),
 }
 
 _lib = None
