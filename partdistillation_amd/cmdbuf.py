@@ -26,14 +26,12 @@ from torch.utils._python_dispatch import TorchDispatchMode
 
 from . import lib as _lib
 
-MAX_ARGS = 48
-LITERAL, STREAM = -1, -2
+MAX_ARGS, LITERAL, STREAM = (_lib.const(n) for n in ("PD_CMD_MAX_ARGS", "PD_CMD_LITERAL", "PD_CMD_STREAM"))
 ENABLED = __import__("os").environ.get("PD_CMDBUF", "1") != "0"
 DEBUG = __import__("os").environ.get("PD_CMDBUF_DEBUG", "0") != "0"
 
 
-class PdCmd(ctypes.Structure):                                       # include/pd_cmdbuf.h
-    _fields_ = [("fn", ctypes.c_int32), ("nargs", ctypes.c_int32), ("a", ctypes.c_uint64 * MAX_ARGS), ("kind", ctypes.c_int16 * MAX_ARGS)]
+PdCmd = _lib.struct("PdCmd")
 
 
 class RecorderError(RuntimeError):

@@ -82,9 +82,7 @@ def conv_wgrad(dz, x, k, stride=1, pad=0, like=None):
     return dw
 
 
-class _Desc(ctypes.Structure):                                      # PdConvWgradDesc (include/pd_conv.h)
-    _fields_ = [("dz", ctypes.c_void_p), ("x", ctypes.c_void_p), ("dw", ctypes.c_void_p), ("db", ctypes.c_void_p)] + \
-               [(n, ctypes.c_int32) for n in ("batch", "hi", "wi", "ci", "ho", "wo", "co", "k", "stride", "pad")] + [("scale", ctypes.c_void_p)]
+_Desc = _lib.struct("PdConvWgradDesc")
 
 
 class _Deferred:

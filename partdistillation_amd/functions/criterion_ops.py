@@ -9,7 +9,7 @@ from torch.autograd import Function
 from .. import lib as _lib
 
 _DT = {torch.float32: 0, torch.bfloat16: 2}
-MAX_K = 40960
+MAX_K = _lib.const("PD_UNCERTAIN_MAX_K")
 ENABLED = __import__("os").environ.get("PD_CRITERION_KERNELS", "1") != "0"      # 0: the torch expressions (tools/ A/B runs)
 
 

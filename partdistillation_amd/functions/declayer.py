@@ -2,7 +2,6 @@
 tensors, no autograd — the building blocks of functions/decoder_core.py's hand-written forward / backward.  GPU only, no fallback.
 
 Reference: transformer_decoder/mask2former_transformer_decoder.py:395-439 (the layer loop), :449-459 (prediction head)."""
-import ctypes
 
 import torch
 
@@ -24,8 +23,7 @@ def supported(C_, ff, cdt):
     return C_ == C and ff == FF and cdt == bf16
 
 
-class _PackDesc(ctypes.Structure):                                  # PdDecPack (include/pd_declayer.h)
-    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("rows", ctypes.c_int32), ("cols", ctypes.c_int32), ("transpose", ctypes.c_int32)]
+_PackDesc = _lib.struct("PdDecPack")
 
 
 _PK = {}

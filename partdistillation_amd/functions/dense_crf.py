@@ -5,7 +5,7 @@ import torch
 
 from .. import lib as _lib
 
-MAX_LABELS = 16
+MAX_LABELS = _lib.const("PD_DCRF_MAX_LABELS")
 
 
 def rank_compress(labels, n_labels):

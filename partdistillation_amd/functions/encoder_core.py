@@ -176,12 +176,7 @@ def _ffn_gemm(x, w, b=None, relu=False):
     return torch.addmm(b, x, w.t()) if b is not None else torch.mm(x, w.t())
 
 
-import ctypes as _ct
-
-
-class _TrProblem(_ct.Structure):                                     # PdTransposeProblem, include/pd_rowwise.h
-    _fields_ = [("src", _ct.c_void_p), ("dst", _ct.c_void_p), ("src_batch_stride", _ct.c_int64), ("src_row_stride", _ct.c_int64),
-                ("batch", _ct.c_int32), ("rows", _ct.c_int32), ("cols", _ct.c_int32), ("reserved", _ct.c_int32)]
+_TrProblem = _lib.struct("PdTransposeProblem")
 
 
 class _Stack:

@@ -3,37 +3,23 @@ and the greedy cover of the box-proposal recall.  Every result is an exact integ
 batch of images (a descriptor table staged through a pinned ring), and none reads anything back to the host.
 
 Bit planes are int64 tensors [n, ceil(H*W / 64)] holding the 64-bit words of pd_eval.h (pixel q = bit q % 64 of word q / 64)."""
-import ctypes
 from functools import partial
 
 import torch
 
+from .. import lib as _lib
 from .grouped_launch import as_u8, launch, ptr, require_cuda
 
 LIMITS = (1, 10, 50, 100, 200)            # AR@k of the proposal evaluator
-MAX_ROWS, MAX_GT = 200, 64
+MAX_ROWS, MAX_GT = _lib.const("PD_EVAL_MAX_ROWS"), _lib.const("PD_EVAL_MAX_GT")
 _cuda = partial(require_cuda, "pd_eval")
 _launch = partial(launch, table_bytes="pd_eval_table_bytes")
 
 
-class PdEvalMaskSet(ctypes.Structure):
-    _fields_ = [("masks", ctypes.c_void_p), ("bits", ctypes.c_void_p), ("area", ctypes.c_void_p), ("n", ctypes.c_int32),
-                ("reserved", ctypes.c_int32), ("hw", ctypes.c_int64)]
-
-
-class PdEvalPairs(ctypes.Structure):
-    _fields_ = [("a", ctypes.c_void_p), ("rows", ctypes.c_void_p), ("b", ctypes.c_void_p), ("inter", ctypes.c_void_p),
-                ("p", ctypes.c_int32), ("g", ctypes.c_int32), ("words", ctypes.c_int64)]
-
-
-class PdEvalConfusion(ctypes.Structure):
-    _fields_ = [("pred_bits", ctypes.c_void_p), ("pred_cls", ctypes.c_void_p), ("gt_bits", ctypes.c_void_p), ("gt_cls", ctypes.c_void_p),
-                ("slot", ctypes.c_void_p), ("pred_n", ctypes.c_int32), ("gt_n", ctypes.c_int32), ("hw", ctypes.c_int64)]
-
-
-class PdEvalRecall(ctypes.Structure):
-    _fields_ = [("inter", ctypes.c_void_p), ("rows", ctypes.c_void_p), ("area_p", ctypes.c_void_p), ("area_g", ctypes.c_void_p),
-                ("p", ctypes.c_int32), ("g", ctypes.c_int32)]
+PdEvalMaskSet = _lib.struct("PdEvalMaskSet")
+PdEvalPairs = _lib.struct("PdEvalPairs")
+PdEvalConfusion = _lib.struct("PdEvalConfusion")
+PdEvalRecall = _lib.struct("PdEvalRecall")
 
 
 def words_of(hw):

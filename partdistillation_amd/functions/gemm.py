@@ -262,9 +262,7 @@ def gemm_wgrad_acc(dy, x, dw, db=None, x3=None, h2=False, y_amax=None, x_amax=No
         _TIMING["wgrad"].append((a, b, (2.0 * M * N * K, 4.0 * (M * N + M * K + N * K), "h2" if h2 else "x3")))
 
 
-class _WgradDesc(ctypes.Structure):                                 # PdGemmWgradDesc (include/pd_gemm.h)
-    _fields_ = [("dY", ctypes.c_void_p), ("X", ctypes.c_void_p), ("dW", ctypes.c_void_p), ("dB", ctypes.c_void_p)] + \
-               [(n, ctypes.c_int32) for n in ("M", "N", "K", "ldy", "ldx", "ldw")] + [("y_amax", ctypes.c_void_p), ("x_amax", ctypes.c_void_p)]
+_WgradDesc = _lib.struct("PdGemmWgradDesc")
 
 
 class WgradQueue:

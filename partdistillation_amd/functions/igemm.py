@@ -11,19 +11,9 @@ GATE_NONE, GATE_RELU, GATE_GELU = 0, 1, 2
 RES_DENSE, RES_UP2 = 0, 1
 
 
-class PdIgemm(ctypes.Structure):                                     # include/pd_igemm.h
-    _fields_ = [(n, ctypes.c_void_p) for n in ("src", "w", "scale", "bias", "res", "res2", "gate", "out", "out_pre")] + \
-               [(n, ctypes.c_int32) for n in ("batch", "hs", "ws", "cs", "ho", "wo", "n", "k", "stride", "pad", "dgrad", "act", "gate_mode", "res_mode", "bias_bf16", "out_col_slab")]
-
-
-class PdFilterTranspose(ctypes.Structure):                           # include/pd_igemm.h
-    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("scale", ctypes.c_void_p), ("co", ctypes.c_int32), ("taps", ctypes.c_int32),
-                ("ci", ctypes.c_int32)]
-
-
-class PdWgrad(ctypes.Structure):                                     # include/pd_igemm.h
-    _fields_ = [("dy", ctypes.c_void_p), ("x", ctypes.c_void_p), ("dw", ctypes.c_void_p), ("db", ctypes.c_void_p), ("row_scale", ctypes.c_void_p)] + \
-               [(n, ctypes.c_int32) for n in ("m", "n", "k", "ldy", "ldx", "ldw", "dw_f32")]
+PdIgemm = _lib.struct("PdIgemm")
+PdFilterTranspose = _lib.struct("PdFilterTranspose")
+PdWgrad = _lib.struct("PdWgrad")
 
 
 _WS = {}
@@ -239,7 +229,7 @@ def wgrad(dy, x, dw=None, db=None, row_scale=None, out_dtype=torch.bfloat16):
     return dw
 
 
-WGRAD_SEQ_MAX = 8                                                    # PD_WGRAD_SEQ_MAX of include/pd_igemm.h
+WGRAD_SEQ_MAX = _lib.const("PD_WGRAD_SEQ_MAX")
 
 
 def wgrad_seq(items):

@@ -1,26 +1,20 @@
 """Per-pixel mask assignment at a resized output and its histogram on the device (include/pd_assign.h, csrc/mask_assign_resized.hip).
 Each function is ONE launch for all images of a batch (descriptor table staged through the pinned ring of functions/grouped_launch.py)
 and reads nothing back to the host."""
-import ctypes
 from functools import partial
 
 import torch
 
+from .. import lib as _lib
 from .grouped_launch import as_u8, launch, require_cuda
 
-MAX_K, MAX_KEYS, MAX_GT = 256, 1024, 64
+MAX_K, MAX_KEYS, MAX_GT = (_lib.const(n) for n in ("PD_ASSIGN_MAX_K", "PD_ASSIGN_MAX_KEYS", "PD_ASSIGN_MAX_GT"))
 _cuda = partial(require_cuda, "pd_assign")
 _launch = partial(launch, table_bytes="pd_assign_table_bytes")
 
 
-class PdAssignResized(ctypes.Structure):
-    _fields_ = [(k, ctypes.c_void_p) for k in ("logits", "scores", "object", "cls_of_query", "arg", "obj", "positive", "cls")] + \
-        [(k, ctypes.c_int32) for k in ("K", "h", "w", "Hp", "Wp", "Hi", "Wi", "H", "W", "reserved")]
-
-
-class PdAssignHistogram(ctypes.Structure):
-    _fields_ = [(k, ctypes.c_void_p) for k in ("key", "obj", "gt", "won", "area", "inter", "gt_area")] + \
-        [("n", ctypes.c_int32), ("G", ctypes.c_int32), ("hw", ctypes.c_int64)]
+PdAssignResized = _lib.struct("PdAssignResized")
+PdAssignHistogram = _lib.struct("PdAssignHistogram")
 
 
 def mask_assign_resized(items):

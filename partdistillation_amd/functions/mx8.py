@@ -14,13 +14,8 @@ GRAD_FORMAT = int(__import__("os").environ.get("PD_MX8_GRAD_FORMAT", E5M2))   # 
                                                      # (activations and weights: e4m3)
 
 
-class PdMx8Gemm(ctypes.Structure):                                   # include/pd_mx8.h
-    _fields_ = [(n, ctypes.c_void_p) for n in ("a_q", "a_s", "w_q", "w_s", "bias", "gate", "out", "out_pre", "out_q", "out_s")] + \
-               [(n, ctypes.c_int32) for n in ("m", "n", "k", "a_format", "act", "gate_mode", "bias_bf16", "out_format")]
-
-
-class PdMx8Tensor(ctypes.Structure):                                 # include/pd_mx8.h
-    _fields_ = [("x", ctypes.c_void_p), ("q", ctypes.c_void_p), ("s", ctypes.c_void_p), ("numel", ctypes.c_int64)]
+PdMx8Gemm = _lib.struct("PdMx8Gemm")
+PdMx8Tensor = _lib.struct("PdMx8Tensor")
 
 
 def supported(m, n, k):

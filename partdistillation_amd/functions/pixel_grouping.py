@@ -1,26 +1,20 @@
 """Label maps and boolean masks of resized evaluation images on the device (include/pd_grouping.h, csrc/pixel_grouping.hip).  Each
 function is ONE launch for all images of a batch (descriptor table staged through the pinned ring of functions/grouped_launch.py) and
 reads nothing back to the host."""
-import ctypes
 from functools import partial
 
 import torch
 
+from .. import lib as _lib
 from .grouped_launch import as_u8, launch, require_cuda
 
-MAX_K = 32
+MAX_K = _lib.const("PD_GROUPING_MAX_K")
 _cuda = partial(require_cuda, "pd_grouping")
 _launch = partial(launch, table_bytes="pd_grouping_table_bytes")
 
 
-class PdGroupLabels(ctypes.Structure):
-    _fields_ = [("scores", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("labels", ctypes.c_void_p), ("counts", ctypes.c_void_p)] + \
-        [(k, ctypes.c_int32) for k in ("K", "h", "w", "Hp", "Wp", "Hi", "Wi", "H", "W", "reserved")]
-
-
-class PdMaskResize(ctypes.Structure):
-    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("area", ctypes.c_void_p)] + \
-        [(k, ctypes.c_int32) for k in ("n", "Hp", "Wp", "Hi", "Wi", "H", "W", "reserved")]
+PdGroupLabels = _lib.struct("PdGroupLabels")
+PdMaskResize = _lib.struct("PdMaskResize")
 
 
 def scores_argmax_resized(items):

@@ -92,11 +92,10 @@ def copy_d2d(dst, src):
     return dst
 
 
-class _CopySeg(ctypes.Structure):                                   # PdCopySeg (include/pd_rowwise.h)
-    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("bytes", ctypes.c_int64)]
+_CopySeg = _lib.struct("PdCopySeg")
 
 
-MAX_COPY_SEGS = 48
+MAX_COPY_SEGS = _lib.const("PD_COPY_MAX_SEGS")
 
 
 def copy_segments(pairs):

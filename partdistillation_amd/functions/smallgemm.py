@@ -70,9 +70,7 @@ def bmm_tn_supported(x, w):
             and (x.shape[1] * w.shape[1]) % 4 == 0)
 
 
-class _TnDesc(ctypes.Structure):                                     # PdSgemmTnDesc (include/pd_smallgemm.h)
-    _fields_ = [("X", ctypes.c_void_p), ("W", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("Y", ctypes.c_void_p)] + \
-               [(n, ctypes.c_int32) for n in ("M", "N", "ldx", "ldw", "ldy")]
+_TnDesc = _lib.struct("PdSgemmTnDesc")
 
 
 def linear_multi(problems):
@@ -149,9 +147,7 @@ def wgrad_split(dy, x, want_bias=True):
 
 
 
-class _WgradDesc(ctypes.Structure):                                  # PdSgemmWgradDesc (include/pd_smallgemm.h)
-    _fields_ = [("dY", ctypes.c_void_p), ("X", ctypes.c_void_p), ("dW", ctypes.c_void_p), ("dB", ctypes.c_void_p)] + \
-               [(n, ctypes.c_int32) for n in ("M", "N", "K", "ldy", "ldx", "ldw")]
+_WgradDesc = _lib.struct("PdSgemmWgradDesc")
 
 
 class WgradQueue:

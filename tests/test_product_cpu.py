@@ -27,7 +27,12 @@ def test_capi_library_loads_and_exports_all_declared_symbols():
     for name in declared:
         assert hasattr(so, name), f"libpd_hip.so does not export {name}"
     assert declared <= set(lib.SIGNATURES)
-    assert lib.load().pd_abi_version() == lib.ABI_VERSION
+    assert set(lib.SIGNATURES) <= declared                              # derived from the same headers: nothing declared elsewhere
+    loaded = lib.load()
+    for name, (res, args) in lib.SIGNATURES.items():                    # every declared function is exported and carries its derived types
+        fn = getattr(loaded, name)
+        assert fn.restype is res and list(fn.argtypes) == args, name
+    assert loaded.pd_abi_version() == lib.ABI_VERSION
 
 
 def test_product_never_imports_oracle():
