@@ -12,12 +12,11 @@
  *   pd_resample_rows_u8   horizontal pass of Pillow's 8-bit resample (Resample.c ImagingResampleHorizontal_8bpc):
  *                         tmp[r][x][c] = clip8((2^21 + sum_k src[row0 + r][col(xmin[x] + k)][c] * kk[x][k]) >> 22),
  *                         col(j) = x0 + j, mirrored (W - 1 - col) when `flip` — flip and first crop are just addressing
- *   pd_resample_cols_u8   vertical pass + second crop + pad + HWC -> CHW:
- *                         out[c][y][x] = y < vh && x < vw ? clip8((2^21 + sum_k tmp[ymin[y] + k - r0][x][c] * kk[y][k]) >> 22) : pad
- *   pd_resample_cols_canvas_u8   the same vertical pass onto a RECTANGULAR out_h x out_w canvas, interleaved or planar: the base
- *                         resize of the mappers (ResizeScale(1, 1, base, base) [+ FixedSizeCrop((base, base))] ahead of the augmentations).
- *                         planar = 0: out[y][x][c], the HWC layout pd_resample_rows_u8 reads, so the base image feeds the next resize
- *                         as it is; planar = 1: out[c][y][x].  Same arithmetic, y >= vh or x >= vw take pad_value.  A canvas has at
+ *   pd_resample_cols_canvas_u8   vertical pass + second crop + pad (+ HWC -> CHW) onto a RECTANGULAR out_h x out_w canvas:
+ *                         y < vh && x < vw ? clip8((2^21 + sum_k tmp[ymin[y] + k - r0][x][c] * kk[y][k]) >> 22) : pad_value,
+ *                         planar = 1: out[c][y][x], what the mappers return; planar = 0: out[y][x][c], the HWC layout
+ *                         pd_resample_rows_u8 reads, so the base resize of the mappers (ResizeScale(1, 1, base, base)
+ *                         [+ FixedSizeCrop((base, base))] ahead of the augmentations) feeds the next resize as it is.  A canvas has at
  *                         least one pixel and sides of at most PD_CANVAS_MAX_SIDE (anything else is PD_ERR_INVALID_ARG, as are
  *                         vh > out_h, vw > out_w, vw > tmp_w, ksize <= 0 and a null pointer that would be read or written), so there is
  *                         no empty request: vh = 0 or vw = 0 launches and fills the canvas with pad_value
@@ -66,9 +65,6 @@ extern "C" {
 
 int pd_resample_rows_u8(const uint8_t *src, int H, int W, int row0, int rows, int x0, int flip, const int32_t *xmin,
                         const int32_t *cnt, const int32_t *kk, int ksize, int out_w, uint8_t *tmp, void *stream);
-
-int pd_resample_cols_u8(const uint8_t *tmp, int tmp_rows, int tmp_w, int r0, const int32_t *ymin, const int32_t *cnt,
-                        const int32_t *kk, int ksize, int vh, int vw, int S, int pad_value, uint8_t *out, void *stream);
 
 #define PD_CANVAS_MAX_SIDE 65535
 int pd_resample_cols_canvas_u8(const uint8_t *tmp, int tmp_rows, int tmp_w, int r0, const int32_t *ymin, const int32_t *cnt,

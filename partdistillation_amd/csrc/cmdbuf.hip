@@ -175,7 +175,6 @@ const Entry kTable[] = {
   PD_E(pd_poly_crossings_i32),
   PD_E(pd_relu_bwd_colsum),
   PD_E(pd_resample_cols_canvas_u8),
-  PD_E(pd_resample_cols_u8),
   PD_E(pd_resample_rows_u8),
   PD_E(pd_resize_bilinear_nhwc_f32),
   PD_E(pd_rle_sample_groups_canvas_u8),

@@ -39,7 +39,7 @@ __global__ __launch_bounds__(256) void resample_rows(const uint8_t *__restrict__
   o[0] = clip8(a0); o[1] = clip8(a1); o[2] = clip8(a2);
 }
 
-// one thread per output pixel of the out_h x out_w canvas (S x S for pd_resample_cols_u8), all 3 channel planes
+// one thread per output pixel of the out_h x out_w canvas, all 3 channel planes
 __global__ __launch_bounds__(256) void resample_cols(const uint8_t *__restrict__ tmp, int tmp_w, int r0, const int32_t *__restrict__ ymin,
                                                      const int32_t *__restrict__ cnt, const int32_t *__restrict__ kk, int ksize, int vh,
                                                      int vw, int out_h, int out_w, int pad_value, uint8_t *__restrict__ out)
@@ -183,17 +183,6 @@ extern "C" int pd_resample_rows_u8(const uint8_t *src, int H, int W, int row0, i
   hipLaunchKernelGGL(resample_rows, dim3((out_w + 255) / 256, rows), dim3(256), 0, (hipStream_t)stream_, src, W, row0, rows, x0, flip,
                      xmin, cnt, kk, ksize, out_w, tmp);
   return pd_check_launch("pd_resample_rows_u8");
-}
-
-extern "C" int pd_resample_cols_u8(const uint8_t *tmp, int tmp_rows, int tmp_w, int r0, const int32_t *ymin, const int32_t *cnt,
-                                   const int32_t *kk, int ksize, int vh, int vw, int S, int pad_value, uint8_t *out, void *stream_)
-{
-  if (S <= 0 || vh < 0 || vw < 0 || vh > S || vw > S || vw > tmp_w || ksize <= 0)
-    return pd_set_error(PD_ERR_INVALID_ARG, "pd_resample_cols_u8: bad sizes S=%d vh=%d vw=%d tmp_w=%d", S, vh, vw, tmp_w);
-  if (!out || (vh > 0 && vw > 0 && (!tmp || !ymin || !cnt || !kk))) return pd_set_error(PD_ERR_INVALID_ARG, "pd_resample_cols_u8: null pointer");
-  hipLaunchKernelGGL(resample_cols, dim3((S + 255) / 256, S), dim3(256), 0, (hipStream_t)stream_, tmp, tmp_w, r0, ymin, cnt, kk, ksize,
-                     vh, vw, S, S, pad_value, out);
-  return pd_check_launch("pd_resample_cols_u8");
 }
 
 extern "C" int pd_resample_cols_canvas_u8(const uint8_t *tmp, int tmp_rows, int tmp_w, int r0, const int32_t *ymin, const int32_t *cnt,

@@ -20,50 +20,39 @@ pd_resample_cols_canvas_u8 writing the HWC canvas the next pd_resample_rows_u8 r
 (data/dataset_mappers/part_distillation_dataset_mapper.py), train and test; both mappers read the saved pseudo-label dicts of the
 PATH_ONLY datasets through `load_annotation`."""
 import logging
-import math
 import os
 
 import numpy as np
 import torch
 
-from .. import lib as _lib
 from ..compat import BitMasks, Instances
+from ..functions.input_pipeline import (base_canvas, base_image, nearest_index, resample_coeffs, resample_u8, rle_sample, upload_image,
+                                        upload_tables)
 from ..utils import rle as _rle
 
-PRECISION_BITS = 32 - 8 - 2
+
+def read_image(record, key="file_name"):
+    """the record's decoded "image", else the file record[key] through Pillow -> uint8 [H, W, 3]"""
+    image = record.get("image")
+    if image is None:
+        from PIL import Image
+        image = np.asarray(Image.open(record[key]).convert("RGB"))
+    return image
 
 
-def resample_coeffs(in_size, out_size, first, count):
-    """Pillow Resample.c precompute_coeffs + normalize_coeffs_8bpc (bilinear) for output indices [first, first + count),
-    vectorised with the same double-precision operation order (the weight sum is a sequential cumsum)."""
-    if in_size == out_size:                                   # Pillow skips the pass: identity taps
-        idx = np.arange(first, first + count, dtype=np.int32)
-        return idx, np.ones(count, dtype=np.int32), np.full((count, 1), 1 << PRECISION_BITS, dtype=np.int32)
-    scale = filterscale = (float(in_size) - 0.0) / out_size
-    if filterscale < 1.0:
-        filterscale = 1.0
-    support = 1.0 * filterscale
-    ksize = int(math.ceil(support)) * 2 + 1
-    ss = 1.0 / filterscale
-    center = 0.0 + (np.arange(first, first + count, dtype=np.float64) + 0.5) * scale
-    xmin = np.maximum((center - support + 0.5).astype(np.int64), 0)
-    xmax = np.minimum((center + support + 0.5).astype(np.int64), in_size) - xmin
-    x = np.arange(ksize, dtype=np.int64)[None, :]
-    arg = np.abs(((x + xmin[:, None]) - center[:, None] + 0.5) * ss)
-    w = np.where((x < xmax[:, None]) & (arg < 1.0), 1.0 - arg, 0.0)
-    ww = np.cumsum(w, axis=1)[:, -1:]
-    k = np.where(ww != 0.0, w / np.where(ww != 0.0, ww, 1.0), w)
-    v = k * (1 << PRECISION_BITS)
-    kk = np.where(v < 0, np.trunc(v - 0.5), np.trunc(v + 0.5)).astype(np.int32)
-    return xmin.astype(np.int32), xmax.astype(np.int32), kk
+def load_cpu(path):
+    return torch.load(path, map_location="cpu", weights_only=False)          # pickled Python objects (dicts, numpy arrays), not tensors only
 
 
-def nearest_index(in_size, out_size):
-    """Pillow NEAREST resize positions (Geometry.c ImagingScaleAffine): tabulated by repeated addition in double precision"""
-    scale = float(in_size) / float(out_size)
-    steps = np.full(out_size, scale, dtype=np.float64)
-    steps[0] = 0.0 + scale * 0.5
-    return np.clip(np.cumsum(steps).astype(np.int64), 0, in_size - 1).astype(np.int32)
+def load_saved(path, logger):
+    """`load_cpu`; None (logged) when the file is corrupted — a missing or unreadable file is not a corrupted one"""
+    try:
+        return load_cpu(path)
+    except OSError:
+        raise
+    except Exception:
+        logger.info("%s is corrupted.", path)
+        return None
 
 
 def random_crop(rng, h, w, crop_type, crop_size):
@@ -115,21 +104,10 @@ class DeviceProposalMapper:
                    device or cfg.MODEL.DEVICE, base_size=base_size, class_code_to_class_id=class_code_to_class_id)
 
     # ------------------------------------------------------------------ host: saved pseudo-labels of the PATH_ONLY datasets
-    def _load_saved(self, path_tuple):
-        """torch.load of dataset_path/class_code/file on the CPU; None (logged) when the file is corrupted"""
-        path = os.path.join(*path_tuple)
-        try:
-            return torch.load(path, map_location="cpu", weights_only=False)      # the dicts hold numpy arrays (part_scores)
-        except OSError:
-            raise                                                                # a missing or unreadable file is not a corrupted one
-        except Exception:
-            self.logger.info("%s is corrupted.", path)
-            return None
-
     def load_annotation(self, path_tuple):
         """reference :113-139: the dict ProposalGenerationModel._result saves -> dataset dict, or None when the file is corrupted, the
         object is not larger than min_object_area_ratio of the image, or there are no part masks"""
-        ann = self._load_saved(path_tuple)
+        ann = load_saved(os.path.join(*path_tuple), self.logger)
         if ann is None or not ann["object_ratio"] > self.min_object_area_ratio or not ann["part_mask"]:
             return None
         h, w = ann["part_mask"][-1]["segmentation"]["size"]
@@ -140,10 +118,7 @@ class DeviceProposalMapper:
     # ------------------------------------------------------------------ host: parameter draws (detectron2 0.6 augmentation_impl.py)
     def base_canvas(self, h, w):
         """ResizeScale(1.0, 1.0, base, base) [+ FixedSizeCrop((base, base))] of an h x w image -> ((bh, bw) resized, (ch, cw) canvas)"""
-        base = self.base_size
-        scale = min(base * 1.0 / h, base * 1.0 / w)
-        bh, bw = int(np.round(h * scale)), int(np.round(w * scale))
-        return (bh, bw), ((base, base) if self.square_base else (bh, bw))
+        return base_canvas(h, w, self.base_size, self.square_base)
 
     def draw(self, in_h, in_w, weak=False):
         """in_h, in_w: the size the augmentations see — the base canvas when the base stage is on"""
@@ -169,77 +144,31 @@ class DeviceProposalMapper:
         return p
 
     # ------------------------------------------------------------------ device: pixels
-    def _dev(self, a):
-        return torch.from_numpy(np.ascontiguousarray(a)).to(self.device, non_blocking=True)
-
-    def _upload(self, image):
-        if self.device.type != "cuda":
-            raise RuntimeError("the device input pipeline runs on the GPU only (no CPU fallback in partdistillation_amd)")
-        img = image if torch.is_tensor(image) else torch.from_numpy(np.ascontiguousarray(image))
-        assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3, img.shape
-        return img.to(self.device, non_blocking=True).contiguous()
-
     def base_image(self, image, planar=False):
-        """image uint8 [H, W, 3] -> the base canvas uint8 [ch, cw, 3] ([3, ch, cw] when `planar`) on the device: Pillow BILINEAR resize
-        to base_canvas(H, W), the rest of the canvas = pad_value"""
-        assert self.base_size > 0, "base_image needs base_size > 0"
-        img = self._upload(image)
-        L, st = _lib.load(), _lib.current_stream()
-        H, W = int(img.shape[0]), int(img.shape[1])
-        (bh, bw), (ch, cw) = self.base_canvas(H, W)
-        ymin, ycnt, ykk = resample_coeffs(H, bh, 0, bh)
-        xmin, xcnt, xkk = resample_coeffs(W, bw, 0, bw)
-        r0, r1 = int(ymin.min()), int((ymin + ycnt).max())
-        tmp = torch.empty((r1 - r0, bw, 3), dtype=torch.uint8, device=self.device)
-        out = torch.empty((3, ch, cw) if planar else (ch, cw, 3), dtype=torch.uint8, device=self.device)
-        tabs = [self._dev(t) for t in (xmin, xcnt, xkk, ymin, ycnt, ykk)]
-        _lib.check(L.pd_resample_rows_u8(img.data_ptr(), H, W, r0, r1 - r0, 0, 0, tabs[0].data_ptr(), tabs[1].data_ptr(), tabs[2].data_ptr(),
-                                         xkk.shape[1], bw, tmp.data_ptr(), st))
-        _lib.check(L.pd_resample_cols_canvas_u8(tmp.data_ptr(), r1 - r0, bw, r0, tabs[3].data_ptr(), tabs[4].data_ptr(), tabs[5].data_ptr(),
-                                                ykk.shape[1], bh, bw, ch, cw, self.pad_value, int(planar), out.data_ptr(), st))
-        return out
+        """image uint8 [H, W, 3] -> the base canvas uint8 [ch, cw, 3] ([3, ch, cw] when `planar`) on the device"""
+        return base_image(image, self.base_size, self.square_base, self.pad_value, planar, self.device)
 
     def transform(self, image, segmentations, p):
         """image uint8 [H, W, 3] (numpy or tensor), segmentations = list of COCO RLE dicts {"size": [H, W], "counts": str}
         -> (image uint8 [3,S,S], masks bool [n,S,S], padding_mask bool [S,S], areas int32 [n]) on the device"""
-        img = self._upload(image)
-        L, S = _lib.load(), p["size"]
-        st = _lib.current_stream()
-        H, W = int(img.shape[0]), int(img.shape[1])
-        (x0, y0, cw, ch), (rh, rw), (ox, oy), flip = p["crop1"], p["resize"], p["crop2"], int(p["flip"])
+        img = upload_image(image, self.device)
+        S, H, W = p["size"], int(img.shape[0]), int(img.shape[1])
+        (x0, y0, cw, ch), (rh, rw), (ox, oy), flip = p["crop1"], p["resize"], p["crop2"], p["flip"]
         vh, vw = min(rh - oy, S), min(rw - ox, S)
         # image: horizontal pass over the source rows the surviving output rows need, then vertical pass + crop + pad
-        ymin, ycnt, ykk = resample_coeffs(ch, rh, oy, vh)
-        xmin, xcnt, xkk = resample_coeffs(cw, rw, ox, vw)
-        r0, r1 = int(ymin.min()), int((ymin + ycnt).max())
-        tmp = torch.empty((r1 - r0, vw, 3), dtype=torch.uint8, device=self.device)
-        out = torch.empty((3, S, S), dtype=torch.uint8, device=self.device)
-        tabs = [self._dev(t) for t in (xmin, xcnt, xkk, ymin, ycnt, ykk)]
-        _lib.check(L.pd_resample_rows_u8(img.data_ptr(), H, W, y0 + r0, r1 - r0, x0, flip, tabs[0].data_ptr(), tabs[1].data_ptr(),
-                                         tabs[2].data_ptr(), xkk.shape[1], vw, tmp.data_ptr(), st))
-        _lib.check(L.pd_resample_cols_u8(tmp.data_ptr(), r1 - r0, vw, r0, tabs[3].data_ptr(), tabs[4].data_ptr(), tabs[5].data_ptr(),
-                                         ykk.shape[1], vh, vw, S, self.pad_value, out.data_ptr(), st))
+        out = resample_u8(img, resample_coeffs(cw, rw, ox, vw), resample_coeffs(ch, rh, oy, vh), (S, S), row0=y0, x0=x0, flip=flip,
+                          pad_value=self.pad_value)
         padding = torch.ones((S, S), dtype=torch.bool, device=self.device)
         padding[:vh, :vw] = False
-        # masks: straight from the run lengths
-        n = len(segmentations)
-        masks = torch.empty((n, S, S), dtype=torch.uint8, device=self.device)
-        area = torch.zeros(n, dtype=torch.int32, device=self.device)
-        if n:
-            starts, offsets = [], [0]
-            for seg in segmentations:
-                assert tuple(seg["size"]) == (H, W), (seg["size"], (H, W))
-                counts = seg["counts"]
-                counts = _rle.string_to_counts(counts) if isinstance(counts, (str, bytes)) else np.asarray(counts)
-                cs = np.concatenate([[0], np.cumsum(counts[:-1])]) if len(counts) else np.zeros(1)
-                starts.append(cs.astype(np.int32))
-                offsets.append(offsets[-1] + len(cs))
-            sx = (x0 + nearest_index(cw, rw)[ox:ox + vw]).astype(np.int32)
-            sy = (y0 + nearest_index(ch, rh)[oy:oy + vh]).astype(np.int32)
-            d = [self._dev(t) for t in (np.concatenate(starts), np.asarray(offsets, dtype=np.int32), sx, sy)]
-            _lib.check(L.pd_rle_sample_u8(d[0].data_ptr(), d[1].data_ptr(), n, H, W, flip, d[2].data_ptr(), d[3].data_ptr(), vh, vw, S,
-                                          masks.data_ptr(), area.data_ptr(), st))
-        return out, masks.view(torch.bool) if n else masks.bool(), padding, area
+        for seg in segmentations:
+            assert tuple(seg["size"]) == (H, W), (seg["size"], (H, W))
+        masks, area = torch.empty((0, S, S), dtype=torch.uint8, device=self.device), torch.zeros(0, dtype=torch.int32, device=self.device)
+        if segmentations:                                                    # masks: straight from the run lengths, one upload
+            sx = x0 + nearest_index(cw, rw)[ox:ox + vw]
+            sy = y0 + nearest_index(ch, rh)[oy:oy + vh]
+            d = upload_tables(_rle.segmentations_to_starts(segmentations, (H, W)) + (sx, sy), self.device)
+            masks, area = rle_sample(d[0], d[1], H, W, flip, d[2], d[3], S)
+        return out, masks.view(torch.bool), padding, area
 
     def select(self, masks, area):
         """reference :217-235: drop empty masks (filter_empty_instances(by_box=False)), then masks whose share of the total
@@ -250,14 +179,6 @@ class DeviceProposalMapper:
             return nonempty
         ratio = a[nonempty] / a[nonempty].sum()
         return nonempty[ratio > self.min_area_ratio]
-
-    @staticmethod
-    def _read_image(dataset_dict):
-        image = dataset_dict.get("image")
-        if image is None:
-            from PIL import Image
-            image = np.asarray(Image.open(dataset_dict["file_name"]).convert("RGB"))
-        return image
 
     def _output(self, dataset_dict, image, padding, masks, classes, size):
         inst = Instances(size)
@@ -276,7 +197,7 @@ class DeviceProposalMapper:
             dataset_dict = self.load_annotation(dataset_dict)
             if dataset_dict is None:
                 return None
-        image = self._read_image(dataset_dict)
+        image = read_image(dataset_dict)
         if self.base_size > 0:
             image = self.base_image(image)                                   # once: it does not depend on the draws
         annos = dataset_dict["pseudo_annotations"]
@@ -319,7 +240,7 @@ class DevicePartDistillationMapper(DeviceProposalMapper):
     def load_annotation(self, path_tuple):
         """reference :130-164: the dict save_generated_part_labels / save_part_segmentation write (part_labels a tensor, part_scores a
         numpy array, part_ratios a tensor or absent) -> dataset dict with the parts that pass the ratio and score filters, or None"""
-        ann = self._load_saved(path_tuple)
+        ann = load_saved(os.path.join(*path_tuple), self.logger)
         if ann is None or not ann["object_ratio"] >= self.min_object_area_ratio or not ann["part_masks"]:
             return None
         parts = []
@@ -346,7 +267,7 @@ class DevicePartDistillationMapper(DeviceProposalMapper):
             if dataset_dict is None:
                 return None
         from ..functions import rle as device_rle
-        image = self.base_image(self._read_image(dataset_dict), planar=True)
+        image = self.base_image(read_image(dataset_dict), planar=True)
         size = (int(image.shape[1]), int(image.shape[2]))
         annos = dataset_dict["pseudo_annotations"]
         classes = torch.tensor([int(a.get("category_id", -1)) for a in annos], dtype=torch.int64, device=self.device)

@@ -10,16 +10,16 @@ Host side (cheap, data-dependent control flow, vectorised numpy): the draws in d
 is not in this image), ResizeShortestEdge.get_output_shape, the box transform and the box half of filter_empty_instances, the run-length
 parse, Pillow's coefficient tables for the surviving window and the group table.  Device side: Pillow's two-pass bilinear resample for the
 rows and columns that survive the crop (pd_resample_rows_u8 with the column tables reversed when flipped, pd_resample_cols_canvas_u8
-planar) and ONE pd_rle_sample_groups_u8 launch per attempt for every mask: the members are the object masks followed by all part masks, the
+planar) and ONE `rle_sample_groups` launch per attempt for every mask: the members are the object masks followed by all part masks, the
 planes each object alone followed by the part planes (one per object and class, or one per part), and the two small count vectors that
 come back decide survival — no dense full-resolution mask, no per-object / per-class loop over planes."""
 import numpy as np
 import torch
 
-from .. import lib as _lib
 from ..compat import BitMasks, Instances
+from ..functions.input_pipeline import nearest_index, resample_coeffs, resample_u8, rle_sample_groups, to_device, upload_image
 from ..utils import rle as _rle
-from .device_mapper import DeviceProposalMapper, nearest_index, random_crop, resample_coeffs
+from .device_mapper import random_crop, read_image
 
 XYXY_ABS, XYWH_ABS = 0, 1                                                    # detectron2 BoxMode values
 
@@ -83,47 +83,6 @@ def group_table(n_obj, part_obj, part_cls, part_ok, merged):
     return offsets, members, np.asarray(g_obj, dtype=np.int64), np.asarray(g_cls, dtype=np.int64)
 
 
-def rle_sample_groups(starts, offsets, H, W, src_x, src_y, group_offsets, group_members, out=None, member_area=None, group_area=None,
-                      uploaded=None, canvas=None):
-    """pd_rle_sample_groups_u8 on device tensors (int32 tables; the group table may be host numpy: its member indices are range-checked
-    here, before upload) -> (planes uint8 [G, out_h, out_w], member_area int32 [n], group_area int32 [G]); nothing is pre-zeroed.
-    `uploaded`: device int32 copies (group_offsets, group_members padded by one entry) of the host group table the caller has already
-    sent with another upload; the host table is still what is checked.
-    `canvas` = (out_h, out_w): pd_rle_sample_groups_canvas_u8 — the tables span the window len(src_y) x len(src_x) in the top-left corner
-    of each plane and the rest of the plane is 0 (ValueError when the window does not fit)"""
-    dev = src_x.device
-    n, G = int(offsets.numel()) - 1, len(group_offsets) - 1
-    go, gm = (np.asarray(a.cpu() if torch.is_tensor(a) else a, dtype=np.int64).reshape(-1) for a in (group_offsets, group_members))
-    if G < 0 or go[0] != 0 or (np.diff(go) < 0).any() or go[-1] != len(gm):
-        raise ValueError("rle_sample_groups: group_offsets is not a CSR offset vector of group_members")
-    if len(gm) and (gm.min() < 0 or gm.max() >= n):
-        raise ValueError(f"rle_sample_groups: member index outside [0, {n})")
-    if uploaded is not None:
-        d_go, d_gm = uploaded
-        assert d_go.dtype == torch.int32 and d_gm.dtype == torch.int32 and d_go.numel() == len(go) and d_gm.numel() > len(gm)
-    else:
-        d_go = torch.from_numpy(go.astype(np.int32)).to(dev, non_blocking=True)
-        d_gm = torch.from_numpy(np.concatenate((gm, [0])).astype(np.int32)).to(dev, non_blocking=True)  # never a null pointer
-    vh, vw = int(src_y.numel()), int(src_x.numel())
-    out_h, out_w = (vh, vw) if canvas is None else (int(canvas[0]), int(canvas[1]))
-    if vh > out_h or vw > out_w:
-        raise ValueError(f"rle_sample_groups: the window {vh} x {vw} does not fit the canvas {out_h} x {out_w}")
-    out = torch.empty((G, out_h, out_w), dtype=torch.uint8, device=dev) if out is None else out
-    member_area = torch.empty(n, dtype=torch.int32, device=dev) if member_area is None else member_area
-    group_area = torch.empty(G, dtype=torch.int32, device=dev) if group_area is None else group_area
-    assert out.is_contiguous() and tuple(out.shape) == (G, out_h, out_w) and member_area.numel() == n and group_area.numel() == G
-    tail = (d_go.data_ptr(), d_gm.data_ptr(), G, out.data_ptr() if G else None, member_area.data_ptr() if n else None,
-            group_area.data_ptr() if G else None, _lib.current_stream())
-    if canvas is None:
-        _lib.check(_lib.load().pd_rle_sample_groups_u8(starts.data_ptr() if n else None, offsets.data_ptr() if n else None, n, H, W,
-                                                       src_x.data_ptr(), src_y.data_ptr(), out_h, out_w, *tail))
-    else:
-        _lib.check(_lib.load().pd_rle_sample_groups_canvas_u8(starts.data_ptr() if n else None, offsets.data_ptr() if n else None, n, H, W,
-                                                              src_x.data_ptr() if vw else None, src_y.data_ptr() if vh else None, vh, vw,
-                                                              out_h, out_w, *tail))
-    return out, member_area, group_area
-
-
 class DeviceGTPartMapper:
     """the work the two reference mappers share; the subclasses hold exactly what differs between them"""
     num_repeats = 100            # attempts with the crop before the pass without it
@@ -184,35 +143,18 @@ class DeviceGTPartMapper:
         return nearest_index(p["in_w"], rw)[cols].astype(np.int32), nearest_index(p["in_h"], rh)[y0:y0 + ch].astype(np.int32)
 
     def _dev(self, a):
-        return torch.from_numpy(np.ascontiguousarray(a)).to(self.device, non_blocking=True)
-
-    def _upload(self, image):
-        if self.device.type != "cuda":
-            raise RuntimeError("the device input pipeline runs on the GPU only (no CPU fallback in partdistillation_amd)")
-        img = image if torch.is_tensor(image) else torch.from_numpy(np.ascontiguousarray(image))
-        assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3, img.shape
-        return img.to(self.device, non_blocking=True).contiguous()
+        return to_device(a, self.device)
 
     # ------------------------------------------------------------------ device: pixels
     def transform_image(self, img, p):
         """img uint8 [H, W, 3] on the device -> uint8 [3, ch, cw]: the window of the Pillow BILINEAR full-size resize that survives
         the crop, mirrored when flipped.  The coefficient tables cover only that window; flipped, they are handed over in reverse."""
-        L, st = _lib.load(), _lib.current_stream()
         H, W = int(img.shape[0]), int(img.shape[1])
         (rh, rw), (x0, y0, cw, ch) = p["resize"], p["crop"]
         xtab = resample_coeffs(W, rw, rw - x0 - cw if p["flip"] else x0, cw)
         if p["flip"]:
-            xtab = tuple(np.ascontiguousarray(t[::-1]) for t in xtab)
-        ytab = resample_coeffs(H, rh, y0, ch)
-        r0, r1 = int(ytab[0].min()), int((ytab[0] + ytab[1]).max())
-        tmp = torch.empty((r1 - r0, cw, 3), dtype=torch.uint8, device=self.device)
-        out = torch.empty((3, ch, cw), dtype=torch.uint8, device=self.device)
-        tabs = [self._dev(t) for t in xtab + ytab]
-        _lib.check(L.pd_resample_rows_u8(img.data_ptr(), H, W, r0, r1 - r0, 0, 0, tabs[0].data_ptr(), tabs[1].data_ptr(), tabs[2].data_ptr(),
-                                         xtab[2].shape[1], cw, tmp.data_ptr(), st))
-        _lib.check(L.pd_resample_cols_canvas_u8(tmp.data_ptr(), r1 - r0, cw, r0, tabs[3].data_ptr(), tabs[4].data_ptr(), tabs[5].data_ptr(),
-                                                ytab[2].shape[1], ch, cw, ch, cw, 0, 1, out.data_ptr(), st))
-        return out
+            xtab = tuple(t[::-1] for t in xtab)
+        return resample_u8(img, xtab, resample_coeffs(H, rh, y0, ch))
 
     # ------------------------------------------------------------------ host: the record
     @staticmethod
@@ -263,7 +205,7 @@ class DeviceGTPartMapper:
             raise NotImplementedError("the (dict, part_file) input of CityscapesPartMapper reads the part ids with panoptic_parts, which is "
                                       "not available: pass records whose annotations / part_annotations are already RLE")
         rec = self.parse(dataset_dict)
-        img = self._upload(DeviceProposalMapper._read_image(dataset_dict))
+        img = upload_image(read_image(dataset_dict), self.device)
         H, W = int(img.shape[0]), int(img.shape[1])
         starts, offsets = _rle.segmentations_to_starts(rec["segs"], (H, W))
         runs = (self._dev(starts), self._dev(offsets))                       # once per image: the runs do not depend on the draws

@@ -8,11 +8,11 @@ reference's dataset registration (register_imagenet.py, register_imagenet_with_p
 and the catalogs stay out.
 
 Both augmentation lists are fixed: [ResizeScale(1, 1, S, S)] for proposal generation, [ResizeScale(1, 1, S, S)] then
-[FixedSizeCrop((S, S))] for part ranking — exactly the base stage of DeviceProposalMapper (device_mapper.py `base_image`), which is reused
-as it is.  Host side: the two draws the transforms consume, the run-length parse and, for proposal generation, which masks are empty and
-the boxes of the others, both straight from the run lengths (no device readback).  Device side: the Pillow-exact two-pass resize
-(pd_resample_rows_u8, pd_resample_cols_canvas_u8), the mask decode of stage 1 (pd_rle_decode) and, for part ranking, ONE
-pd_rle_sample_groups_canvas_u8 launch (include/pd_input.h) that ORs every part straight from its run lengths into the window of the
+[FixedSizeCrop((S, S))] for part ranking — exactly the base stage of DeviceProposalMapper: the same `base_canvas` / `base_image`
+(functions/input_pipeline.py).  Host side: the two draws the transforms consume, the run-length parse and, for proposal generation,
+which masks are empty and the boxes of the others, both straight from the run lengths (no device readback).  Device side: the
+Pillow-exact two-pass resize (`resample_u8`), the mask decode of stage 1 (pd_rle_decode) and, for part ranking, ONE
+`rle_sample_groups(canvas=)` launch (include/pd_input.h) that ORs every part straight from its run lengths into the window of the
 S x S plane the resized image occupies and zeroes the rest — the reference's `FixedSizeCrop` pad of n dense masks followed by
 `gt_masks.tensor.sum(0)[None]`, without the n dense planes.  Nothing is read back and nothing synchronises.
 
@@ -26,20 +26,14 @@ import numpy as np
 import torch
 
 from ..compat import BitMasks, Instances
-from ..utils import rle as _rle
-from .device_mapper import DeviceProposalMapper
-from .gt_part_mapper import rle_sample_groups
+from ..functions.input_pipeline import base_canvas, base_image, pack_tables, rle_sample_groups, to_device
+from ..utils.rle import run_lengths, segmentations_to_starts
+from .device_mapper import load_saved, read_image
 
 _logger = logging.getLogger("part_distillation")
 
 
 # ---------------------------------------------------------------------------------------------------- host: run lengths
-def run_lengths(segmentation):
-    """COCO RLE dict (counts as str / bytes / run lengths) -> run lengths int64, the first a run of zeros"""
-    counts = segmentation["counts"]
-    return _rle.string_to_counts(counts) if isinstance(counts, (str, bytes)) else np.asarray(counts, dtype=np.int64).reshape(-1)
-
-
 def run_area(counts):
     """set pixels of a mask = the sum of its odd-indexed run lengths"""
     return int(np.asarray(counts)[1::2].sum())
@@ -63,17 +57,6 @@ def run_box(counts, h):
 
 
 # ---------------------------------------------------------------------------------------------------- host: records
-def _load(path):
-    """torch.load on the CPU; None (logged) when the file is corrupted — a missing or unreadable file is not a corrupted one"""
-    try:
-        return torch.load(path, map_location="cpu", weights_only=False)
-    except OSError:
-        raise
-    except Exception:
-        _logger.info("%s is corrupted.", path)
-        return None
-
-
 def imagenet_record(dataset_path, class_code, image_name, class_code_to_class_id, class_name=None, object_mask_path=None):
     """the dict of the reference's register_imagenet.py:43-57 for dataset_path/class_code/image_name.  With `object_mask_path`
     (PROPOSAL_GENERATION.WITH_GIVEN_MASK) the Detic file object_mask_path/class_code/image_name gives the single pseudo-annotation: its
@@ -84,7 +67,7 @@ def imagenet_record(dataset_path, class_code, image_name, class_code_to_class_id
         path = os.path.join(object_mask_path, class_code, image_name)
         if not os.path.exists(path):
             return None
-        object_data = _load(path)
+        object_data = load_saved(path, _logger)
         if object_data is None or len(object_data["object_masks"]) == 0:
             return None
         data["pseudo_annotations"] = [{"segmentation": object_data["object_masks"][0]["segmentation"]}]
@@ -94,7 +77,7 @@ def imagenet_record(dataset_path, class_code, image_name, class_code_to_class_id
 def imagenet_proposal_record(path_tuple, class_code_to_class_id, min_object_area_ratio=-1.0):
     """the dict of the reference's register_imagenet_with_proposals.py:54-75 from the file (dataset_path, class_code, name) that
     ProposalGenerationModel saved; None when the file is corrupted, `object_ratio` is not above the threshold or `part_mask` is empty"""
-    ann = _load(os.path.join(*path_tuple))
+    ann = load_saved(os.path.join(*path_tuple), _logger)
     if ann is None or not ann["object_ratio"] > min_object_area_ratio or not ann["part_mask"]:
         return None
     h, w = ann["part_mask"][-1]["segmentation"]["size"]
@@ -115,7 +98,7 @@ class DeviceProposalGenerationMapper:
     def __init__(self, image_size, with_given_mask=False, device="cuda", rng=None):
         self.image_size, self.with_given_mask, self.device = int(image_size), bool(with_given_mask), torch.device(device)
         self.rng = rng if rng is not None else np.random                     # detectron2 draws from the global numpy RNG
-        self._base = DeviceProposalMapper(self.image_size, device=device, rng=self.rng, base_size=self.image_size, square_base=False)
+        self.square_base, self.pad_value = False, 128                       # no canvas beyond the resized image: nothing is padded
         self.logger = _logger
 
     @classmethod
@@ -126,17 +109,6 @@ class DeviceProposalGenerationMapper:
     def draw(self):
         """ResizeScale(1.0, 1.0, S, S) draws its scale"""
         self.rng.uniform(1.0, 1.0)
-
-    @staticmethod
-    def _read_image(record):
-        image = record.get("image")
-        if image is None:
-            try:
-                from PIL import Image
-                image = np.asarray(Image.open(record["file_path"]).convert("RGB"))
-            except Exception:                                               # the reference: a bare `except: return`
-                return None
-        return image
 
     def masks(self, record):
         """the host half of `_transform_annotations` (:79-106): the non-empty masks' segmentations, classes (-1 when absent) and float32
@@ -156,9 +128,12 @@ class DeviceProposalGenerationMapper:
         """record: `imagenet_record`'s dict, with "image" (decoded uint8 HWC) or a "file_path" readable by Pillow -> the reference
         mapper's output dict, tensors on the device: image uint8 [3, h, w], height / width = h, w and, with `with_given_mask`,
         instances (gt_masks BitMasks, gt_classes int64, gt_boxes float32 [k, 4])"""
-        image = self._read_image(record)
+        image = record.get("image")
         if image is None:
-            return None
+            try:
+                image = read_image(record, "file_path")
+            except Exception:                                               # the reference: a bare `except: return`
+                return None
         if "width" in record or "height" in record:                         # detection_utils.check_image_size
             if (record.get("height"), record.get("width")) != (image.shape[0], image.shape[1]):
                 raise ValueError(f"Mismatched image shape for {record.get('file_path')}: got {(image.shape[0], image.shape[1])}, "
@@ -170,15 +145,15 @@ class DeviceProposalGenerationMapper:
             if not segs:
                 self.logger.info("No mask detected on {}.".format(record.get("file_path")))
                 return None
-        img = self._base.base_image(image, planar=True)
+        img = base_image(image, self.image_size, self.square_base, self.pad_value, True, self.device)
         h, w = int(img.shape[1]), int(img.shape[2])
         out.update(image=img, height=h, width=w)
         if self.with_given_mask:
             from ..functions import rle as device_rle
             inst = Instances((h, w))
             inst.gt_masks = BitMasks(device_rle.decode_masks(segs, segs[0]["size"], self.device))
-            inst.gt_classes = self._base._dev(classes)
-            inst.gt_boxes = self._base._dev(boxes)
+            inst.gt_classes = to_device(classes, self.device)
+            inst.gt_boxes = to_device(boxes, self.device)
             out["instances"] = inst
         return out
 
@@ -194,8 +169,7 @@ class DeviceImagenetPartRankingMapper:
         self.image_size, self.device = int(image_size), torch.device(device)
         self.class_code_to_class_index = class_code_to_class_index
         self.rng = rng if rng is not None else np.random                     # detectron2 draws from the global numpy RNG
-        self._base = DeviceProposalMapper(self.image_size, device=device, rng=self.rng, pad_value=pad_value, base_size=self.image_size,
-                                          square_base=True)
+        self.square_base, self.pad_value = True, int(pad_value)
 
     @classmethod
     def from_config(cls, cfg, class_code_to_class_index, device=None):
@@ -215,19 +189,19 @@ class DeviceImagenetPartRankingMapper:
         """everything the sampling launch reads, as ONE int32 vector and its split points: the run starts and their offsets, the identity
         index tables of the bh x bw window, and the group table of the single plane that holds every member (padded by one entry)"""
         n = len(segmentations)
-        starts, offsets = _rle.segmentations_to_starts(segmentations, (bh, bw))
+        starts, offsets = segmentations_to_starts(segmentations, (bh, bw))
         parts = (starts, offsets, np.arange(bw, dtype=np.int32), np.arange(bh, dtype=np.int32), np.asarray([0, n], dtype=np.int32),
                  np.arange(n + 1, dtype=np.int32) % max(n, 1))
-        return np.concatenate(parts).astype(np.int32), np.cumsum([len(p) for p in parts])[:-1]
+        return pack_tables(parts)
 
     def __call__(self, record):
         """record: `imagenet_proposal_record`'s dict, with "image" (decoded uint8 HWC) or a "file_name" readable by Pillow -> the
         reference mapper's output dict, tensors on the device: image uint8 [3, S, S], height = width = S, instances (gt_masks BitMasks
         [1, S, S], gt_classes int64 [1])"""
         S = self.image_size
-        image = DeviceProposalMapper._read_image(record)
+        image = read_image(record)
         self.draw()
-        (bh, bw), _ = self._base.base_canvas(int(image.shape[0]), int(image.shape[1]))
+        (bh, bw), _ = base_canvas(int(image.shape[0]), int(image.shape[1]), S, self.square_base)
         segs = [part["segmentation"] for part in record["pseudo_annotations"]]
         name = record.get("file_name")
         if not segs:
@@ -237,15 +211,15 @@ class DeviceImagenetPartRankingMapper:
                 raise ValueError(f"{name}: a part mask of size {tuple(int(v) for v in seg['size'])} on an image resized to {(bh, bw)}: "
                                  f"the part masks must have the size of the resized image")
         class_index = self.class_code_to_class_index[record["class_code"]]
-        img = self._base.base_image(image, planar=True)
+        img = base_image(image, self.image_size, self.square_base, self.pad_value, True, self.device)
         table, cuts = self.tables(segs, bh, bw)
-        d = self._base._dev(table)                                          # one upload
+        d = to_device(table, self.device)                                        # one upload
         starts, offsets, sx, sy, d_go, d_gm = torch.tensor_split(d, cuts.tolist())
         n = len(segs)
         plane = rle_sample_groups(starts, offsets, bh, bw, sx, sy, [0, n], np.arange(n), uploaded=(d_go, d_gm), canvas=(S, S))[0]
         inst = Instances((S, S))
         inst.gt_masks = BitMasks(plane.view(torch.bool))
-        inst.gt_classes = self._base._dev(np.asarray([class_index], dtype=np.int64))
+        inst.gt_classes = to_device(np.asarray([class_index], dtype=np.int64), self.device)
         out = {k: v for k, v in record.items() if k not in ("pseudo_annotations", "image")}
         out.update(image=img, height=S, width=S, instances=inst)
         return out

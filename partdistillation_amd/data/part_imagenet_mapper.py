@@ -9,7 +9,7 @@ train mode.  Host side: the draws, the vertex transform in float64, the float32 
 filter_empty_instances (for PolygonMasks the mask half is always true, so SURVIVAL IS DECIDED BY BOXES ALONE: the retry loop launches
 nothing and nothing is read back), the exact table offsets and the group table.  Device side, once per image: the Pillow-exact image
 resample (pd_resample_rows_u8, pd_resample_cols_canvas_u8), ONE pd_poly_crossings_i32 for the polygons of the surviving parts and ONE
-pd_rle_sample_groups_u8 with identity index tables that ORs them into planes: plane 0 = all members (the object), then one plane per
+`rle_sample_groups` with identity index tables that ORs them into planes: plane 0 = all members (the object), then one plane per
 unique class (USE_MERGED_GT) or per surviving part.  One small upload carries the vertices and every table; there is no synchronisation.
 
 UNPINNED: pycocotools and detectron2 are not available to test against; the rasteriser and the draw order are restatements
@@ -23,8 +23,9 @@ import torch
 
 from ..compat import BitMasks, Instances
 from ..functions import polygon as _poly
-from .device_mapper import DeviceProposalMapper
-from .gt_part_mapper import DeviceGTPartMapper, boxes_nonempty, rle_sample_groups
+from ..functions.input_pipeline import rle_sample_groups, upload_image
+from .device_mapper import load_cpu, read_image
+from .gt_part_mapper import DeviceGTPartMapper, boxes_nonempty
 
 MAPPING_22K = "metadata/imagenet1k_to_22k_mapping.pkl"
 
@@ -73,7 +74,7 @@ class DevicePartImageNetMapper(DeviceGTPartMapper):
             if not os.path.exists(MAPPING_22K):
                 raise FileNotFoundError(f"{MAPPING_22K} is needed to map the ImageNet-1k class ids to the 22k vocabulary of "
                                         f"DATASETS.TRAIN[0] = '{train[0]}'")
-            to_22k = torch.load(MAPPING_22K, map_location="cpu", weights_only=False)
+            to_22k = load_cpu(MAPPING_22K)
             table = {k: to_22k[i] for k, i in table.items()}
         return cls(is_train, *cls._resize_args(cfg, is_train), cfg.CUSTOM_DATASETS.USE_MERGED_GT, cfg.MODEL.DEVICE,
                    class_code_to_class_id=table)
@@ -141,7 +142,7 @@ class DevicePartImageNetMapper(DeviceGTPartMapper):
     # ------------------------------------------------------------------ device: the masks
     def rasterize(self, polys, h, w, group_offsets, group_members):
         """polys: the member polygons at the h x w output -> planes uint8 [G, h, w].  One upload (vertices, polygon offsets, table offsets,
-        identity index tables, group table), pd_poly_crossings_i32, pd_rle_sample_groups_u8; nothing comes back (the two pixel-count
+        identity index tables, group table), pd_poly_crossings_i32, `rle_sample_groups`; nothing comes back (the two pixel-count
         vectors the sampling also writes are not read: survival was decided by the boxes)"""
         if self.device.type != "cuda":
             raise RuntimeError("the device input pipeline runs on the GPU only (no CPU fallback in partdistillation_amd)")
@@ -162,7 +163,7 @@ class DevicePartImageNetMapper(DeviceGTPartMapper):
                 raise ValueError(f"{file_name}: no annotation with iscrowd == 0 (the reference mapper crashes on such a record in train mode)")
             return None
         object_class = self.class_code_to_class_id[class_code]
-        img = self._upload(DeviceProposalMapper._read_image(dict(dataset_dict, file_name=file_name)))
+        img = upload_image(read_image(dict(dataset_dict, file_name=file_name)), self.device)
         H, W = int(img.shape[0]), int(img.shape[1])
         attempts = self.num_repeats if self.is_train else 1
         for attempt in range(attempts + (1 if self.is_train else 0)):

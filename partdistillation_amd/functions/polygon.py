@@ -2,7 +2,7 @@
 itself is UNPINNED: it is not available to test against).  The host does what is integer bookkeeping — the (int)(5 x + .5) upsample of
 the vertices, the EXACT number of boundary positions of every polygon (a closed form of the upsampled end points of its edges) and the
 CSR offsets that follow — so the kernel needs no count pass and nothing is read back; the device computes and sorts the positions.  A
-polygon's table is in the run-starts format of include/pd_input.h: `rle_sample_groups` (data/gt_part_mapper.py) turns tables into planes,
+polygon's table is in the run-starts format of include/pd_input.h: `rle_sample_groups` (functions/input_pipeline.py) turns tables into planes,
 a group of several polygons into their OR.  GPU only; there is no fallback."""
 import numpy as np
 import torch

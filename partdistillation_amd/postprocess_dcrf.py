@@ -1,11 +1,11 @@
 """Dense-CRF clean-up of generated part proposals: the loop body of the reference's continuously_postprocess_dcrf.py:127-153 with the
 mean field on the device (functions/dense_crf.py).  The image is brought to size x size the way the reference does (ResizeScale(1, 1, size,
-size) + FixedSizeCrop(size), padded with 128) through DeviceProposalMapper's Pillow-exact image path."""
+size) + FixedSizeCrop(size), padded with 128) through the mappers' Pillow-exact base stage (functions/input_pipeline.py `base_image`)."""
 import numpy as np
 import torch
 
-from .data.device_mapper import DeviceProposalMapper
 from .functions import dense_crf as _dcrf
+from .functions.input_pipeline import base_image
 from .utils import rle
 
 MASK_KEYS = ("part_masks", "part_mask")          # the reference's key; the key ProposalGenerationModel._result writes
@@ -13,10 +13,7 @@ MASK_KEYS = ("part_masks", "part_mask")          # the reference's key; the key 
 
 def resize_image(image, size=640, device="cuda"):
     """uint8 [H, W, 3] (numpy or tensor) -> uint8 [size, size, 3] on the device"""
-    mapper = DeviceProposalMapper(size, 1.0, 1.0, flip=False, device=device, rng=np.random.RandomState(0))   # no draw decides anything
-    img = image if torch.is_tensor(image) else torch.from_numpy(np.ascontiguousarray(image))
-    out, _, _, _ = mapper.transform(img, [], mapper.draw(int(img.shape[0]), int(img.shape[1])))
-    return out.permute(1, 2, 0).contiguous()
+    return base_image(image, size, True, 128, False, device)
 
 
 def refine_proposals(data, image, size=640, device="cuda", **crf):

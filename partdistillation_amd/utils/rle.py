@@ -143,6 +143,12 @@ def run_table_to_coco_json(offsets, starts, values, size) -> list:
     return out
 
 
+def run_lengths(segmentation):
+    """COCO RLE dict (counts as str / bytes / run lengths) -> run lengths int64, the first a run of zeros"""
+    counts = segmentation["counts"]
+    return string_to_counts(counts) if isinstance(counts, (str, bytes)) else np.asarray(counts, dtype=np.int64).reshape(-1)
+
+
 def segmentations_to_starts(segmentations, size):
     """list[COCO RLE dict] (counts as str / bytes / run lengths) -> (starts, offsets) int32, pd_rle_sample_u8's format: for mask i the
     entries [offsets[i], offsets[i + 1]) of starts are the exclusive prefix sums of its run lengths.  ValueError when a mask's size differs
@@ -152,8 +158,7 @@ def segmentations_to_starts(segmentations, size):
     for seg in segmentations:
         if tuple(int(v) for v in seg["size"]) != size:
             raise ValueError(f"tensor shapes do not match. ({size} != {tuple(int(v) for v in seg['size'])})")
-        counts = seg["counts"]
-        counts = string_to_counts(counts) if isinstance(counts, (str, bytes)) else np.asarray(counts, dtype=np.int64)
+        counts = run_lengths(seg)
         cs = np.concatenate(([0], np.cumsum(counts[:-1]))) if len(counts) else np.zeros(1)
         starts.append(cs.astype(np.int32))
         offsets.append(offsets[-1] + len(cs))

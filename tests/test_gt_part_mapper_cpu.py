@@ -234,7 +234,7 @@ def test_sample_groups_rejects_bad_arguments_before_any_launch():
 
 def test_wrapper_checks_the_member_range_before_upload():
     import torch
-    from partdistillation_amd.data.gt_part_mapper import rle_sample_groups
+    from partdistillation_amd.functions.input_pipeline import rle_sample_groups
     z = torch.zeros(4, dtype=torch.int32)
     offsets = torch.tensor([0, 1, 2], dtype=torch.int32)                   # two members
     for members in ([0, 2], [-1, 0]):

@@ -16,7 +16,7 @@ DEV = "cuda"
 # ------------------------------------------------------------------------------------------------ the kernel alone
 def _sample(masks, sx, sy, groups, garbage=7):
     """masks bool [n, H, W] (or (H, W) with n = 0) -> the kernel's three outputs as numpy; the outputs are pre-filled with garbage"""
-    from partdistillation_amd.data.gt_part_mapper import rle_sample_groups
+    from partdistillation_amd.functions.input_pipeline import rle_sample_groups
     from partdistillation_amd.utils import rle
     if isinstance(masks, tuple):
         (H, W), segs = masks, []
@@ -85,7 +85,7 @@ def test_sample_groups_odd_pitches_and_wave_edges(out_w, out_h):
 
 @pytest.mark.parametrize("kind", ["descending", "repeats_7_to_20", "gaps_40_to_9"])
 def test_sample_groups_index_tables(kind):
-    from partdistillation_amd.data.device_mapper import nearest_index
+    from partdistillation_amd.functions.input_pipeline import nearest_index
     rng = np.random.RandomState(len(kind))
     W = {"descending": 23, "repeats_7_to_20": 7, "gaps_40_to_9": 40}[kind]
     H = 17

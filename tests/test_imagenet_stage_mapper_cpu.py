@@ -62,7 +62,7 @@ def test_canvas_entry_rejects_bad_arguments_before_any_launch():
 
 
 def test_wrapper_refuses_a_window_larger_than_the_canvas():
-    from partdistillation_amd.data.gt_part_mapper import rle_sample_groups
+    from partdistillation_amd.functions.input_pipeline import rle_sample_groups
     z = torch.zeros(4, dtype=torch.int32)
     offsets = torch.tensor([0, 1, 2], dtype=torch.int32)
     for canvas in ((3, 9), (9, 3)):
@@ -77,7 +77,7 @@ def test_from_config_on_the_shipped_yamls():
         cfg = _cfg(yaml)
         m = DeviceProposalGenerationMapper.from_config(cfg)
         assert (m.image_size, m.with_given_mask, m.device.type) == (cfg.INPUT.IMAGE_SIZE, False, "cpu")
-        assert (m._base.base_size, m._base.square_base) == (m.image_size, False)
+        assert (m.image_size, m.square_base) == (cfg.INPUT.IMAGE_SIZE, False)
         m = DeviceProposalGenerationMapper.from_config(_cfg(yaml, ["INPUT.IMAGE_SIZE", "640", "PROPOSAL_GENERATION.WITH_GIVEN_MASK", "True"]))
         assert (m.image_size, m.with_given_mask) == (640, True)
     table = {"n01": 3}
@@ -85,7 +85,7 @@ def test_from_config_on_the_shipped_yamls():
     assert cfg.MODEL.META_ARCHITECTURE == "PartRankingModel" and cfg.INPUT.MASK_FORMAT == "bitmask"
     m = DeviceImagenetPartRankingMapper.from_config(cfg, table)
     assert (m.image_size, m.device.type, m.class_code_to_class_index) == (640, "cpu", table)
-    assert (m._base.base_size, m._base.square_base, m._base.pad_value) == (640, True, 128)
+    assert (m.image_size, m.square_base, m.pad_value) == (640, True, 128)
     assert DeviceImagenetPartRankingMapper.from_config(cfg, table, device="cuda").device.type == "cuda"
 
 

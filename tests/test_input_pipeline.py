@@ -66,7 +66,7 @@ def test_oracle_rle_decode_round_trips_the_product_encoder():
 
 def test_product_tables_equal_oracle_loops():
     from oracle import input_pipeline_ref as R
-    from partdistillation_amd.data import device_mapper as D
+    from partdistillation_amd.functions import input_pipeline as D
     rng = np.random.RandomState(2)
     for _ in range(60):
         a, b = rng.randint(3, 1300), rng.randint(3, 1300)

@@ -102,6 +102,37 @@ def test_base_canvas_sizes():
         m.base_image(np.zeros((8, 8, 3), np.uint8))
 
 
+def test_free_base_canvas_is_the_mappers():
+    from partdistillation_amd.data import DeviceProposalMapper
+    from partdistillation_amd.functions.input_pipeline import base_canvas, base_image
+    for H, W, base in [(90, 120, 64), (120, 90, 64), (64, 64, 64), (20, 30, 300), (333, 500, 48), (375, 500, 640)]:
+        for square in (False, True):
+            m = DeviceProposalMapper(64, device="cpu", base_size=base, square_base=square)
+            assert base_canvas(H, W, base, square) == m.base_canvas(H, W)
+    with pytest.raises(RuntimeError, match="GPU only"):
+        base_image(np.zeros((8, 8, 3), np.uint8), 64, True, 128, False, "cpu")
+
+
+def test_resample_tables_travel_as_one_int32_buffer():
+    """the six tables of a resample in one vector: views of vw, vw, vw * ksize_x, vh, vh, vh * ksize_y entries, in that order"""
+    from partdistillation_amd.functions.input_pipeline import pack_tables, resample_coeffs
+    xtab, ytab = resample_coeffs(17, 23, 5, 9), resample_coeffs(11, 7, 2, 4)                  # ksize 3 and 5
+    table, cuts = pack_tables(xtab + ytab)
+    assert table.dtype == np.int32 and table.ndim == 1 and len(cuts) == 5
+    views = torch.tensor_split(torch.from_numpy(table), cuts.tolist())                        # what upload_tables does on the device
+    assert [v.numel() for v in views] == [9, 9, 9 * 3, 4, 4, 4 * 5] and all(v.dtype == torch.int32 for v in views)
+    for v, t in zip(views, xtab + ytab):
+        assert np.array_equal(v.numpy(), np.asarray(t).reshape(-1))
+    flipped = tuple(t[::-1] for t in xtab)                                                    # reversed views pack like copies
+    assert np.array_equal(pack_tables(flipped + ytab)[0][:9], xtab[0][::-1])
+
+
+def test_the_square_column_pass_entry_is_retired():
+    from partdistillation_amd import lib
+    assert lib.load().pd_cmd_fn_index(b"pd_resample_cols_u8") == -1 and "pd_resample_cols_u8" not in lib.SIGNATURES
+    assert not hasattr(lib.load(), "pd_resample_cols_u8")
+
+
 # ------------------------------------------------------------------------------------------------ load_annotation
 def _masks(h=12, w=16):
     m = np.zeros((3, h, w), bool)

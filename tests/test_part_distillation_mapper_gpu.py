@@ -48,7 +48,7 @@ CASES = {
 
 @pytest.mark.parametrize("case", sorted(CASES))
 def test_cols_canvas_kernel_against_numpy(case):
-    from partdistillation_amd.data.device_mapper import resample_coeffs
+    from partdistillation_amd.functions.input_pipeline import resample_coeffs
     src_rows, res_rows, first, tmp_w, vw, out_h, out_w, planar = CASES[case]
     vh = min(res_rows - first, out_h)
     ymin, cnt, kk = resample_coeffs(src_rows, res_rows, first, vh)
@@ -71,7 +71,7 @@ def test_cols_canvas_kernel_against_numpy(case):
 @pytest.mark.parametrize("planar", [0, 1])
 def test_cols_canvas_kernel_all_pad_and_bad_arguments(planar):
     from partdistillation_amd import lib
-    from partdistillation_amd.data.device_mapper import resample_coeffs
+    from partdistillation_amd.functions.input_pipeline import resample_coeffs
     ymin, cnt, kk = resample_coeffs(8, 12, 0, 12)
     tmp = np.random.RandomState(1).randint(0, 256, (8, 9, 3)).astype(np.uint8)
     got = _cols_call(tmp, 0, ymin, cnt, kk, 0, 9, 12, 300, 77, planar)                                # vh = 0: an all-pad canvas

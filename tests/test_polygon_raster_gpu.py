@@ -147,7 +147,7 @@ def test_comb_tables_around_the_lds_capacity_and_the_other_thresholds():
 @pytest.mark.parametrize("w", [5, 63, 64, 65, 257])
 def test_tables_through_rle_sample_groups(w):
     """two overlapping polygons ORed in one plane, each alone, an empty group; identity index tables; odd pitches"""
-    from partdistillation_amd.data.gt_part_mapper import rle_sample_groups
+    from partdistillation_amd.functions.input_pipeline import rle_sample_groups
     from partdistillation_amd.functions.polygon import rasterize_polygons
     h = 9
     a = np.asarray([0.2, 0.6, 0.7 * w, 1.3, 0.55 * w, 8.4, 0.1 * w, 6.0])

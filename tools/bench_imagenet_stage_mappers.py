@@ -12,7 +12,7 @@ import numpy as np
 import torch
 from partdistillation_amd import lib
 from partdistillation_amd.data import DeviceImagenetPartRankingMapper, DeviceProposalGenerationMapper
-from partdistillation_amd.data.gt_part_mapper import rle_sample_groups
+from partdistillation_amd.functions.input_pipeline import base_canvas, rle_sample_groups, to_device
 from partdistillation_amd.functions import rle as device_rle
 from partdistillation_amd.utils import rle
 
@@ -29,7 +29,7 @@ H, W, S, N_PART, N_REC = 375, 500, 640, 8, 16
 rng = np.random.RandomState(0)
 ranking = DeviceImagenetPartRankingMapper(S, {"n0123": 0}, rng=np.random.RandomState(1))
 generation = DeviceProposalGenerationMapper(S, True, rng=np.random.RandomState(1))
-(BH, BW), _ = ranking._base.base_canvas(H, W)
+(BH, BW), _ = base_canvas(H, W, S, True)
 
 
 def part_masks(n):
@@ -57,7 +57,7 @@ for i in range(N_REC):
 def new_route(record):
     s = [a["segmentation"] for a in record["pseudo_annotations"]]
     table, cuts = ranking.tables(s, BH, BW)
-    starts, offsets, sx, sy, d_go, d_gm = torch.tensor_split(ranking._base._dev(table), cuts.tolist())
+    starts, offsets, sx, sy, d_go, d_gm = torch.tensor_split(to_device(table, "cuda"), cuts.tolist())
     return rle_sample_groups(starts, offsets, BH, BW, sx, sy, [0, len(s)], np.arange(len(s)), uploaded=(d_go, d_gm), canvas=(S, S))[0]
 
 
