@@ -7,7 +7,9 @@
  * scores and arg-maxes; the IoUs with the ground-truth parts then need one pass over the map per mask.  Here one kernel interpolates the
  * low-resolution logits twice inside the pass that consumes them, and one kernel counts everything the matching needs in one pass.
  *
- * Both kernels serve ALL images of a batch in ONE launch: the caller passes a host list of descriptors, a pinned staging buffer and a
+ * pd_pair_assign_resized is the assignment for (query, class) pairs that share logit maps (the class-aware branches of inference.py).
+ *
+ * Every kernel serves ALL images of a batch in ONE launch: the caller passes a host list of descriptors, a pinned staging buffer and a
  * device buffer of pd_assign_table_bytes(count) bytes each (the pinned one must stay untouched until the asynchronous copy has
  * executed).  All other pointers are device pointers; `stream` = hipStream_t; returns 0 or PD_ERR_* (pd_msda.h) with pd_last_error() set.
  * Nothing is launched when a descriptor is invalid.
@@ -22,7 +24,8 @@ extern "C" {
 #endif
 
 #define PD_ASSIGN_MAX_K 256           /* selected queries per image (TEST.DETECTIONS_PER_IMAGE) */
-#define PD_ASSIGN_MAX_KEYS 1024       /* keys of pd_assign_histogram (queries or classes) */
+#define PD_ASSIGN_MAX_Q 1024          /* queries that the pairs of pd_pair_assign_resized refer to */
+#define PD_ASSIGN_MAX_KEYS 1024      /* keys of pd_assign_histogram (queries or classes) */
 #define PD_ASSIGN_MAX_GT 64           /* ground-truth masks per image (= PD_EVAL_MAX_GT) */
 
 int64_t pd_assign_table_bytes(int32_t count);
@@ -55,6 +58,31 @@ typedef struct PdAssignResized {
   int32_t reserved;
 } PdAssignResized;
 int pd_mask_assign_resized(const PdAssignResized *list, int32_t count, void *table_host_pinned, void *table_device, void *stream);
+
+/*
+ * pd_mask_assign_resized for K (query, class) PAIRS that share queries: the class-aware evaluation branches select the top K of the
+ * Q x nc scores, so several pairs read one mask-logit map.  Pair k stands for logits[pair_query[k]]; every output is bit-identical to
+ * pd_mask_assign_resized run on the gathered stack logits[pair_query] (first maximum in pair order, the identity-size branch and
+ * segments without an object pixel included), but no [K, h, w] copy is made and a workgroup interpolates every REFERENCED query once
+ * (row mix, the 4 x 4 taps, the sigmoid) and then walks that query's pairs for the products scores[k] * sigmoid(v).
+ * logits fp32 [Q, h, w] contiguous, 1 <= Q <= PD_ASSIGN_MAX_Q; pair_query int32 [K] (device) with values in [0, Q): the range is the
+ * caller's contract (a pair outside it never wins a pixel and counts nothing); scores fp32 [K]; cls_of_pair nullable int32 [K] with
+ * values in [-1, 32767]; object nullable uint8 [H, W]; arg int16 [H, W] holds the PAIR index; positive int32 [K] (zero on entry):
+ * positive[k] += #pixels with v > 0 for the query of pair k; cls = obj ? cls_of_pair[arg] : -1.  1 <= K <= PD_ASSIGN_MAX_K.
+ */
+typedef struct PdAssignPairs {
+  const float *logits;
+  const int32_t *pair_query;
+  const float *scores;
+  const int32_t *cls_of_pair;
+  const uint8_t *object;
+  int16_t *arg;
+  uint8_t *obj;
+  int32_t *positive;
+  int16_t *cls;
+  int32_t K, Q, h, w, Hp, Wp, Hi, Wi, H, W;
+} PdAssignPairs;
+int pd_pair_assign_resized(const PdAssignPairs *list, int32_t count, void *table_host_pinned, void *table_device, void *stream);
 
 /*
  * One pass over an assignment map `key` (arg, or cls: int16 [hw]), its object map and the G ground-truth masks (uint8 [G, hw]):

@@ -9,11 +9,13 @@ from .. import lib as _lib
 from .grouped_launch import as_u8, launch, require_cuda
 
 MAX_K, MAX_KEYS, MAX_GT = (_lib.const(n) for n in ("PD_ASSIGN_MAX_K", "PD_ASSIGN_MAX_KEYS", "PD_ASSIGN_MAX_GT"))
+MAX_Q = _lib.const("PD_ASSIGN_MAX_Q")
 _cuda = partial(require_cuda, "pd_assign")
 _launch = partial(launch, table_bytes="pd_assign_table_bytes")
 
 
 PdAssignResized = _lib.struct("PdAssignResized")
+PdAssignPairs = _lib.struct("PdAssignPairs")
 PdAssignHistogram = _lib.struct("PdAssignHistogram")
 
 
@@ -60,6 +62,57 @@ def mask_assign_resized(items):
                            Wp=int(Wp), Hi=int(Hi), Wi=int(Wi), H=H, W=W))
         off += K
     _launch("pd_mask_assign_resized", PdAssignResized, fields, (), dev)
+    return out
+
+
+def pair_assign_resized(items):
+    """mask_assign_resized for (query, class) pairs that share queries, without the gathered [K, h, w] copy.
+    items: [(logits fp32 [Q, h, w], pair_query int32 [K] with values in [0, Q) (the caller's contract), scores fp32 [K],
+    object bool / uint8 [H, W] or None, cls_of_pair int32 [K] or None, (Hp, Wp), (Hi, Wi), (H, W))] ->
+    [(arg int16 [H, W] (pair index), obj uint8 [H, W], positive int32 [K], cls int16 [H, W] or None)], bit-identical to
+    mask_assign_resized on logits[pair_query]."""
+    if not items:
+        return []
+    dev = items[0][0].device
+    for it in items:
+        _cuda(it[0], "logits")
+    ktot = sum(int(it[1].numel()) for it in items)
+    positive = torch.zeros(max(ktot, 1), dtype=torch.int32, device=dev)
+    fields, keep, out, off = [], [], [], 0
+    for logits, pq, scores, obj_in, cop, (Hp, Wp), (Hi, Wi), (H, W) in items:
+        if logits.dtype != torch.float32 or logits.dim() != 3 or scores.dtype != torch.float32 or scores.dim() != 1:
+            raise ValueError(f"pair_assign_resized: fp32 logits [Q, h, w] and fp32 scores [K] expected, got {logits.dtype} {tuple(logits.shape)}, "
+                             f"{scores.dtype} {tuple(scores.shape)}")
+        Q, h, w = (int(s) for s in logits.shape)
+        K, H, W = int(scores.numel()), int(H), int(W)
+        _cuda(scores, "scores")
+        _cuda(pq, "pair_query")
+        if pq.dtype != torch.int32 or pq.dim() != 1 or pq.numel() != K:
+            raise ValueError(f"pair_assign_resized: pair_query must be int32 [{K}], got {pq.dtype} {tuple(pq.shape)}")
+        logits, scores, pq = logits.contiguous(), scores.contiguous(), pq.contiguous()
+        o8 = None
+        if obj_in is not None:
+            _cuda(obj_in, "object mask")
+            o8 = as_u8(obj_in, "pair_assign_resized: object mask")
+            if tuple(o8.shape) != (H, W):
+                raise ValueError(f"pair_assign_resized: object mask {tuple(o8.shape)} is not at the output size {(H, W)}")
+        if cop is not None:
+            _cuda(cop, "cls_of_pair")
+            if cop.dtype != torch.int32 or cop.numel() != K:
+                raise ValueError(f"pair_assign_resized: cls_of_pair must be int32 [{K}], got {cop.dtype} {tuple(cop.shape)}")
+            cop = cop.contiguous()
+        arg = torch.empty((H, W), dtype=torch.int16, device=dev)
+        obj = torch.empty((H, W), dtype=torch.uint8, device=dev)
+        cls = torch.empty((H, W), dtype=torch.int16, device=dev) if cop is not None else None
+        keep += [logits, scores, pq, o8, cop]
+        out.append((arg, obj, positive[off:off + K], cls))
+        fields.append(dict(logits=logits.data_ptr(), pair_query=pq.data_ptr(), scores=scores.data_ptr(),
+                           cls_of_pair=None if cop is None else cop.data_ptr(), object=None if o8 is None else o8.data_ptr(),
+                           arg=arg.data_ptr(), obj=obj.data_ptr(), positive=positive.data_ptr() + 4 * off,
+                           cls=None if cls is None else cls.data_ptr(), K=K, Q=Q, h=h, w=w, Hp=int(Hp), Wp=int(Wp), Hi=int(Hi), Wi=int(Wi),
+                           H=H, W=W))
+        off += K
+    _launch("pd_pair_assign_resized", PdAssignPairs, fields, (), dev)
     return out
 
 

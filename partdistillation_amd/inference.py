@@ -6,8 +6,10 @@ multiplies by the object mask, takes sigmoid, scales by the scores and arg-maxes
 Here (per-pixel-unique post-processing, the shipped default, no output resize) `pd_mask_assign` interpolates the
 low-resolution logits inside the single pass that consumes them and writes an int16 arg-max map, the object map and the
 per-query positive-pixel counts; areas, the validity filters and the IoUs with the ground-truth parts are histogram
-counts over that map (exact integers, IoU in float64 like pycocotools).  Other settings take the dense route with torch
-ops on the device."""
+counts over that map (exact integers, IoU in float64 like pycocotools).  A resized output, and the per-pixel-unique
+branches of PartDistillationModel and PartRankingModel below, go through inference_fused.py in the same way, a batch at a
+time.  Other settings (plain thresholding, CPU tensors, sizes past the kernels' limits, PD_FUSED_INFERENCE=0) take the
+dense route with torch ops on the device."""
 import torch
 import torch.nn.functional as F
 
@@ -123,17 +125,27 @@ def inference(model, batched_inputs, targets, images, outputs, vis=False):
         logits_all = materialize_masks(dict(outputs))["pred_masks"]
     pad_hw = tuple(images.tensor.shape[-2:])
     topk = model.wandb_vis_topk if vis and not model.use_unique_per_pixel_label else model.test_topk_per_image
-    results = []
-    for cls, low, tgt, inp, size in zip(outputs["pred_logits"], logits_all, targets, batched_inputs, images.image_sizes):
+    results, resized, fused = [], None, False
+    if model.use_unique_per_pixel_label and logits_all.is_cuda:
+        from . import inference_fused
+        fused = inference_fused.enabled()
+    if fused:                                                 # the images whose output is resized: one launch for all of them
+        which = [b for b, (inp, size) in enumerate(zip(batched_inputs, images.image_sizes))
+                 if (inp.get("height", size[0]), inp.get("width", size[1])) != tuple(size)]
+        resized = inference_fused.proposal_fused(model, batched_inputs, targets, images, outputs["pred_logits"], logits_all, which)
+    for b, (cls, low, tgt, inp, size) in enumerate(zip(outputs["pred_logits"], logits_all, targets, batched_inputs, images.image_sizes)):
         height, width = inp.get("height", size[0]), inp.get("width", size[1])
-        tm = sem_seg_postprocess(tgt["masks"].float(), size, height, width).bool()
-        to = sem_seg_postprocess(tgt["object_masks"].float(), size, height, width).bool()
-        if model.use_unique_per_pixel_label and (height, width) == tuple(size) and low.is_cuda:
-            masks, scores, labels = instance_inference_fused(model, cls, low, pad_hw, (height, width), tm, to, tgt["labels"], topk)
+        if resized is not None and b in resized:
+            masks, scores, labels, tm = resized[b]
         else:
-            dense = F.interpolate(low[None].float(), size=pad_hw, mode="bilinear", align_corners=False)[0]
-            dense = sem_seg_postprocess(dense, size, height, width)
-            masks, scores, labels = instance_inference_dense(model, cls, dense, tm, to, tgt["labels"], topk)
+            tm = sem_seg_postprocess(tgt["masks"].float(), size, height, width).bool()
+            to = sem_seg_postprocess(tgt["object_masks"].float(), size, height, width).bool()
+            if fused and (height, width) == tuple(size):
+                masks, scores, labels = instance_inference_fused(model, cls, low, pad_hw, (height, width), tm, to, tgt["labels"], topk)
+            else:
+                dense = F.interpolate(low[None].float(), size=pad_hw, mode="bilinear", align_corners=False)[0]
+                dense = sem_seg_postprocess(dense, size, height, width)
+                masks, scores, labels = instance_inference_dense(model, cls, dense, tm, to, tgt["labels"], topk)
         if masks.shape[0] == 0:                               # does not contribute to the evaluation (:398-402)
             masks = torch.zeros((1, height, width), dtype=torch.bool, device=low.device)
             scores, labels = scores.new_zeros(1), labels.new_zeros(1)
@@ -220,6 +232,12 @@ def pd_inference(model, batched_inputs, targets, images, outputs, vis=False):
     if logits_all is None:
         from .modeling.transformer_decoder.mask2former_transformer_decoder import materialize_masks
         logits_all = materialize_masks(dict(outputs))["pred_masks"]
+    if model.use_unique_per_pixel_label and logits_all.is_cuda:
+        from . import inference_fused
+        if inference_fused.enabled():
+            res = inference_fused.pd_fused(model, batched_inputs, targets, images, outputs["pred_logits"], logits_all, vis=vis)
+            if res is not None:                               # (None: a limit of the kernels does not hold)
+                return res
     pad_hw = tuple(images.tensor.shape[-2:])
     results = []
     for cls, low, tgt, inp, size in zip(outputs["pred_logits"], logits_all, targets, batched_inputs, images.image_sizes):
@@ -353,6 +371,15 @@ def rank_inference(model, batched_inputs, targets, images, outputs, vis=False):
     feats_all = outputs[model.proposal_key].float()
     if model.proposal_features_norm:
         feats_all = F.normalize(feats_all, p=2, dim=-1)
+    cluster = model.mode == "cluster"
+    if logits_all.is_cuda and (model.use_unique_per_pixel_label_during_clustering if cluster else
+                               model.use_unique_per_pixel_label_during_labeling):
+        from . import inference_fused
+        if inference_fused.enabled():
+            args = (model, batched_inputs, targets, images, outputs["pred_logits"], logits_all, feats_all)
+            res = inference_fused.rank_cluster_fused(*args) if cluster else inference_fused.rank_label_fused(*args, vis=vis)
+            if res is not None:                               # (None: a limit of the kernels does not hold)
+                return res
     pad_hw = tuple(images.tensor.shape[-2:])
     results = []
     for cls, low, feats, tgt, inp, size in zip(outputs["pred_logits"], logits_all, feats_all, targets, batched_inputs, images.image_sizes):

@@ -12,6 +12,7 @@ SKIP = {"pd_abi_version", "pd_conv_bf16_supported", "pd_igemm_bf16_supported", "
 # the table has never held them; cmdbuf.hip does not include pd_assign.h, pd_dcrf.h, pd_eval.h or pd_rle.h.  Move a name out of here,
 # and add its #include there, when a recorded region starts to call it.
 UNRECORDED = {"pd_assign_histogram", "pd_mask_assign_resized", "pd_masks_resize_u8", "pd_scores_argmax_resized_u8", "pd_dec_split",
+              "pd_pair_assign_resized",
               "pd_dcrf_argmax", "pd_dcrf_bilateral_update", "pd_dcrf_prepare", "pd_dcrf_spatial_message",
               "pd_eval_confusion_grouped", "pd_eval_intersect_grouped", "pd_eval_pack_grouped", "pd_eval_recall_grouped",
               "pd_rle_decode", "pd_rle_plane_runs", "pd_rle_seg_rows"}
