@@ -8,8 +8,13 @@
  * of host time per call to pick it); these kernels cut the same product into 32 x 128 tiles so 14..128 workgroups share
  * it, take bias / ReLU / ReLU-mask / bias-gradient in the same pass, and are launched directly.
  *
- * All matrices row-major bf16 with leading dimensions in ELEMENTS (multiples of 8, 16-byte aligned bases); fp32
- * accumulation on v_mfma_f32_32x32x8_bf16_1k; results rounded to nearest even.  `stream` = hipStream_t; 0 or PD_ERR_*.
+ * All matrices row-major bf16 with 16-byte aligned bases and leading dimensions in ELEMENTS:
+ *   the products (tn / nn, their split, batched and multi forms): ldx, ldw, ldy multiples of 8 (operand rows are read, and with
+ *     N or K % 4 == 0 results written, in 16- and 8-byte pieces);
+ *   the weight gradients (wgrad, wgrad_split, wgrad_grouped): ldy and ldx multiples of 8, ldw a multiple of 4 (what a contiguous
+ *     [N, K] gradient with K % 4 == 0 has).
+ * Anything else is PD_ERR_INVALID_ARG before any launch.  fp32 accumulation on v_mfma_f32_32x32x8_bf16_1k; results rounded
+ * ONCE, to nearest even (a bias or an accumulate-base is added in fp32 before that rounding).  `stream` = hipStream_t; 0 or PD_ERR_*.
  */
 #ifndef PD_SMALLGEMM_H
 #define PD_SMALLGEMM_H
@@ -68,7 +73,7 @@ int pd_decoder_head_bf16(const float *tgt, const float *ln_w, const float *ln_b,
                          int B, int C, void *stream);
 
 /* dW[N,K] = dY[M,N]^T . X[M,K];  dB[N] (fp32, nullable) = column sums of dY       nn.Linear weight / bias gradient.
- * Any M >= 0 (rows past M count as zeros); N % 4 == 0, K % 4 == 0. */
+ * Any M >= 0 (rows past M count as zeros; M = 0 writes zeros); N % 4 == K % 4 == ldw % 4 == 0. */
 int pd_sgemm_wgrad_bf16(const void *dY, const void *X, void *dW, float *dB, int M, int N, int K, int ldy, int ldx, int ldw,
                         void *stream);
 
@@ -83,7 +88,8 @@ int pd_sgemm_wgrad_split_bf16(const void *dY, const void *X, void *dW, float *dB
 /* MANY pd_sgemm_wgrad_bf16 problems as one launch (the decoder's backward pass queues its ~70 weight gradients and runs them at
  * its end: a single one is a 7 us launch on a handful of CUs).  descs: host array; table_host_pinned / table_device: caller-
  * provided staging of pd_sgemm_wgrad_grouped_table_bytes(count) bytes each — the function fills the pinned one, copies it with
- * an asynchronous memcpy on `stream`, launches; the pinned buffer must stay untouched until the copy has executed. */
+ * an asynchronous memcpy on `stream`, launches; the pinned buffer must stay untouched until the copy has executed.
+ * Every descriptor obeys pd_sgemm_wgrad_bf16's rules; one with N == 0 or K == 0 is skipped. */
 typedef struct PdSgemmWgradDesc {
   const void *dY, *X;
   void *dW;

@@ -927,9 +927,9 @@ extern "C" int pd_sgemm_nn_bf16(const void *dY, const void *W, const void *relu_
 extern "C" int pd_sgemm_wgrad_bf16(const void *dY, const void *X, void *dW, float *dB, int M, int N, int K, int ldy, int ldx,
                                    int ldw, void *stream_)
 {
-  int rc = check_common("pd_sgemm_wgrad_bf16", M > 0 ? dY : dW, M > 0 ? X : dW, dW, M, N, K, ldy, ldx, 8);
+  int rc = check_common("pd_sgemm_wgrad_bf16", M > 0 ? dY : dW, M > 0 ? X : dW, dW, M, N, K, ldy, ldx, 8);   // ldw: % 4 is enough (a contiguous [N, K] gradient), checked below
   if (rc) return rc;
-  if ((N & 3) || (K & 3)) return pd_set_error(PD_ERR_INVALID_ARG, "pd_sgemm_wgrad_bf16: N=%d and K=%d must be multiples of 4", N, K);
+  if ((N & 3) || (K & 3) || (ldw & 3)) return pd_set_error(PD_ERR_INVALID_ARG, "pd_sgemm_wgrad_bf16: N=%d, K=%d, ldw=%d must be multiples of 4", N, K, ldw);
   if (N == 0 || K == 0) return PD_OK;
   const dim3 g((K + 127) / 128, (N + 31) / 32), b(256);
   hipLaunchKernelGGL(sgemm_wgrad, g, b, 0, (hipStream_t)stream_, (const bf16_t *)dY, (const bf16_t *)X, (bf16_t *)dW, dB, M, N, K, ldy, ldx, ldw);
@@ -983,7 +983,8 @@ extern "C" int pd_sgemm_wgrad_grouped_bf16(const PdSgemmWgradDesc *descs, int co
     const PdSgemmWgradDesc &d = descs[i];
     int rc = check_common("pd_sgemm_wgrad_grouped_bf16", d.M > 0 ? d.dY : d.dW, d.M > 0 ? d.X : d.dW, d.dW, d.M, d.N, d.K, d.ldy, d.ldx, 8);
     if (rc) return rc;
-    if ((d.N & 3) || (d.K & 3)) return pd_set_error(PD_ERR_INVALID_ARG, "pd_sgemm_wgrad_grouped_bf16: N=%d and K=%d must be multiples of 4", d.N, d.K);
+    if ((d.N & 3) || (d.K & 3) || (d.ldw & 3))
+      return pd_set_error(PD_ERR_INVALID_ARG, "pd_sgemm_wgrad_grouped_bf16: N=%d, K=%d, ldw=%d must be multiples of 4", d.N, d.K, d.ldw);
     if (d.N == 0 || d.K == 0) continue;
     SgWgradProblem &q = tab[n++];
     q.dY = (const bf16_t *)d.dY; q.X = (const bf16_t *)d.X; q.dW = (bf16_t *)d.dW; q.dB = d.dB;
