@@ -78,18 +78,19 @@ const Entry kTable[] = {
   PD_E(pd_affine_act_bwd_bf16),
   PD_E(pd_affine_act_fwd_bf16),
   PD_E(pd_attn_bwd_d32),
+  PD_E(pd_attn_bwd_d32_ld),
   PD_E(pd_attn_fwd_d32),
+  PD_E(pd_attn_fwd_d32_ld),
   PD_E(pd_attn_mask_u8),
   PD_E(pd_cast_bf16_f32_amax),
   PD_E(pd_colsum_acc),
   PD_E(pd_conv3x3_nhwc_f16x2),
-  PD_E(pd_conv3x3_nhwc_f32x3),
   PD_E(pd_conv3x3_wgrad_nhwc_f16x2),
-  PD_E(pd_conv3x3_wgrad_nhwc_f32x3),
   PD_E(pd_conv_bf16_dgrad),
   PD_E(pd_conv_bf16_fwd),
   PD_E(pd_conv_bf16_wgrad),
   PD_E(pd_conv_bf16_wgrad_grouped),
+  PD_E(pd_copy_segments),
   PD_E(pd_dec_bwd_a),
   PD_E(pd_dec_bwd_b),
   PD_E(pd_dec_fwd_a),
@@ -100,10 +101,6 @@ const Entry kTable[] = {
   PD_E(pd_gemm_tn_f16x2),
   PD_E(pd_gemm_tn_f16x2_bf16out),
   PD_E(pd_gemm_tn_f32),
-  PD_E(pd_gemm_tn_f32x3),
-  PD_E(pd_gemm_tn_f32x3_pre),
-  PD_E(pd_gemm_tn_f32x3_relu_bits),
-  PD_E(pd_gemm_tn_f32x3_relumask),
   PD_E(pd_gemm_wgrad_acc_f16x2_ws),
   PD_E(pd_gemm_wgrad_acc_f32),
   PD_E(pd_gemm_wgrad_acc_f32x3),
@@ -130,15 +127,8 @@ const Entry kTable[] = {
   PD_E(pd_mask_assign),
   PD_E(pd_mask_point_losses_bwd),
   PD_E(pd_mask_point_losses_fwd),
-  PD_E(pd_matcher_costs),
-  PD_E(pd_copy_segments),
-  PD_E(pd_attn_fwd_d32_ld),
-  PD_E(pd_attn_bwd_d32_ld),
   PD_E(pd_match_point_logits),
-  PD_E(pd_swin_merge_ln_fwd),
-  PD_E(pd_swin_tail_ln_fwd),
-  PD_E(pd_swin_tail_ln_bwd),
-  PD_E(pd_swin_merge_ln_bwd),
+  PD_E(pd_matcher_costs),
   PD_E(pd_matcher_point_terms),
   PD_E(pd_maxpool3s2_bwd_bf16),
   PD_E(pd_maxpool3s2_fwd_bf16),
@@ -193,13 +183,16 @@ const Entry kTable[] = {
   PD_E(pd_sgemm_wgrad_split_bf16),
   PD_E(pd_skinny_linear_bwd),
   PD_E(pd_skinny_linear_fwd),
-  PD_E(pd_split3_bf16),
   PD_E(pd_stem7x7_fwd),
   PD_E(pd_stem7x7_wgrad),
   PD_E(pd_sum3_sum2_f32),
   PD_E(pd_sumsq_accumulate),
   PD_E(pd_swin_ln_bwd),
   PD_E(pd_swin_ln_fwd),
+  PD_E(pd_swin_merge_ln_bwd),
+  PD_E(pd_swin_merge_ln_fwd),
+  PD_E(pd_swin_tail_ln_bwd),
+  PD_E(pd_swin_tail_ln_fwd),
   PD_E(pd_transpose_batched_f32),
   PD_E(pd_uncertain_points),
   PD_E(pd_upsample2x_bwd_nhwc_f32),

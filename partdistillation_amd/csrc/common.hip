@@ -34,7 +34,6 @@ extern "C" int pd_abi_version(void) { return PD_ABI_VERSION; }
 extern int g_pd_dbg_atomic_scope;
 extern int g_pd_dbg_force_generic;
 extern int g_pd_dbg_ablate;
-extern int g_pd_dbg_x3_narrow;
 extern int g_pd_dbg_f16x2;
 extern int g_pd_dbg_wgrad_wide;
 extern "C" void pd_dbg_set_wgrad_xcd(int v);
@@ -46,7 +45,6 @@ extern int g_pd_dbg_bwd_threads;
 extern int g_pd_dbg_attn_scalar;
 extern int g_pd_dbg_wattn;
 extern int g_pd_dbg_wattn_chunk;
-extern int g_pd_dbg_x3;
 extern int g_pd_dbg_kmeans;
 extern int g_pd_dbg_conv_group_rows;
 extern int g_pd_dbg_conv_xcd_major;
@@ -86,12 +84,10 @@ extern "C" int pd_debug_set(const char *key, int value)
   if (!strcmp(key, "sgemm_deep")) { g_pd_dbg_sgemm_deep = value; return PD_OK; }
   if (!strcmp(key, "conv_group_rows")) { g_pd_dbg_conv_group_rows = value; return PD_OK; }
   if (!strcmp(key, "conv_xcd_major")) { g_pd_dbg_conv_xcd_major = value; return PD_OK; }
-  if (!strcmp(key, "x3_ablate")) { g_pd_dbg_x3 = value; return PD_OK; }
   if (!strcmp(key, "f16x2_tile")) { g_pd_dbg_f16x2 = value; return PD_OK; }
   if (!strcmp(key, "wgrad_wide")) { g_pd_dbg_wgrad_wide = value; return PD_OK; }
   if (!strcmp(key, "wgrad_xcd")) { pd_dbg_set_wgrad_xcd(value); return PD_OK; }
   if (!strcmp(key, "wgrad_fast")) { pd_dbg_set_wgrad_fast(value); return PD_OK; }
-  if (!strcmp(key, "x3_narrow")) { g_pd_dbg_x3_narrow = value; return PD_OK; }
   if (!strcmp(key, "wattn_ablate")) { g_pd_dbg_wattn = value; return PD_OK; }
   if (!strcmp(key, "wattn_chunk")) {
     if (value < 0 || value > 8) return pd_set_error(PD_ERR_INVALID_ARG, "pd_debug_set: wattn_chunk is 0 (automatic) or 1..8, got %d", value);

@@ -1,19 +1,16 @@
-// fp32 GEMM on the bf16 matrix cores: every fp32 operand element is split EXACTLY into three bf16 values
+// fp32 weight gradients on the bf16 / fp16 matrix cores.  Three-plane form: every fp32 operand element is split EXACTLY into
+// three bf16 values
 //     x = hi + mid + lo,   hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid)     (3 x 8 significand bits = fp32's 24)
 // when a tile is staged in LDS, and a product a*b is accumulated in fp32 as six bf16 MFMA terms
 //     lo_a hi_b + hi_a lo_b + mid_a mid_b + mid_a hi_b + hi_a mid_b + hi_a hi_b
 // (each bf16 x bf16 product is exact in fp32; the three dropped terms mid*lo, lo*mid, lo*lo are <= 2^-23 |a b| together —
 // the size of ONE fp32 rounding of the product).  v_mfma_f32_32x32x16_bf16 runs 16 x the rate of v_mfma_f32_32x32x2_f32,
-// so six of them per step are 2.7x the exact-fp32 matrix rate: the fp32 Linears of the deformable-attention encoder
-// (reference msdeformattn.py:120-135, forced fp32 by :318) get matrix-core speed without giving up fp32 results
-// (measured against fp64 in tests/test_gemm_gpu.py: error at the level of the library's fp32 GEMM).
-//
-//   gemm_tn_f32x3   C[M,N] = A[M,K] B[N,K]^T (+bias)(ReLU)   128 x 128 x 16 tiles, 4 waves (2x2) x (2x2) MFMA tiles
-// Two LDS stages of three bf16 planes per operand; the next tile's global loads are issued before the MFMAs of the
-// current one, split and written to the other stage after them (one barrier per 16-wide step).
+// so six of them per step are 2.7x the exact-fp32 matrix rate (measured against fp64 in tests/test_gemm_gpu.py: error at the
+// level of the library's fp32 GEMM).  Two-plane form (H2): the fp16 split of f16x2.h, three products per term.
+// The forward / input-gradient products that once lived here in the three-plane form (128 x 128 and 256 x 256 tiles, ReLU-bit and
+// pre-split epilogues) are retired: gemm_f16x2.hip carries every such product.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <type_traits>
 
 #include "f16x2.h"
 #include "mfma_bf16.h"
@@ -25,7 +22,7 @@
 namespace {
 using namespace pdmfma;
 
-constexpr int BM = 128, BN = 128, BK = 16, PITCH = BK + 4;      // bf16 elements per LDS row (40 bytes: 8-byte reads of 32 rows conflict-free)
+constexpr int BM = 128, BN = 128;                                // output tile of the 128 x 128 kernels
 
 struct Split4 { uint2 hi, mid, lo; };                            // 4 consecutive k of one row, per plane
 
@@ -43,370 +40,13 @@ __device__ __forceinline__ Split4 split4(float4 v)
   split2(v.z, v.w, s.hi.y, s.mid.y, s.lo.y);
   return s;
 }
-typedef __bf16 hwbf16x8 __attribute__((ext_vector_type(8)));
-// operand of v_mfma_f32_32x32x16_bf16 (the gfx950 double-K form: 32 cycles per SIMD, twice the rate of the 32x32x8 form):
-// lane l holds 8 consecutive k of row l % 32, starting at 8 * (l / 32) of the 16-wide step.  Two 8-byte LDS reads (the
-// 72-byte row pitch is conflict-free for those).
-__device__ __forceinline__ hwbf16x8 frag(const bf16_t *p)
-{
-  union { uint2 h[2]; hwbf16x8 v; } u;
-  u.h[0] = *reinterpret_cast<const uint2 *>(p);
-  u.h[1] = *reinterpret_cast<const uint2 *>(p + 4);
-  return u.v;
-}
+typedef __bf16 hwbf16x8 __attribute__((ext_vector_type(8)));   // operand of v_mfma_f32_32x32x16_bf16: 8 consecutive contraction elements per lane
 __device__ __forceinline__ void mma16k(f32x16 &c, hwbf16x8 x, hwbf16x8 y) { c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x, y, c, 0, 0, 0); }
 
 __device__ __forceinline__ int xcd_chunk(int bid, int nb) { return pd_xcd_chunk(bid, nb); }   // xcd.h: any workgroup count
 
 __device__ int g_wgrad_xcd = 1;   // tools only (pd_debug_set "wgrad_xcd" 0: launch order = logical order)
 __device__ int g_wgrad_fast = 1;  // tools only (pd_debug_set "wgrad_fast" 0: the guarded step everywhere)
-__device__ __forceinline__ bool v_never(float x) { return x == 1.2345678e30f; }
-
-// CONV: A is an NHWC image [*, H, W, Ci] and row m of the GEMM is output pixel m of a 3 x 3, stride 1, pad 1 convolution:
-// K = 9 Ci ordered (tap, channel) like the channels-last filter [Co][3][3][Ci]; a 16-wide k-step lies inside one tap, so the
-// A tile of a step is the input at pixel m + dy W + dx (zeros outside the image) — an implicit GEMM, nothing is unfolded.
-template <bool RELU, int ABL, bool CONV>
-__global__ __launch_bounds__(256, 2) void gemm_tn_f32x3(const float *__restrict__ A, const float *__restrict__ B,
-                                                         const float *__restrict__ bias, float *__restrict__ C, int M, int N,
-                                                         int K, int lda, int ldb, int ldc, int ntiles_n, int H, int W)
-{
-  __shared__ __attribute__((aligned(16))) bf16_t As[2][3][BM][PITCH];      // two stages x three planes
-  __shared__ __attribute__((aligned(16))) bf16_t Bs[2][3][BN][PITCH];
-  const int lb = xcd_chunk(blockIdx.x, gridDim.x);
-  const int m0 = (lb / ntiles_n) * BM, n0 = (lb % ntiles_n) * BN;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
-  const int lr = t >> 2, lk = (t & 3) * 4;                       // rows lr + 64 j, columns lk .. lk+3 of both tiles
-  float4 ra[2][2], rb[2][2];                                     // two register stages: loads run two steps ahead of their use
-  int py[2], px[2];                                              // CONV: image row / column of this thread's two A rows
-  if (CONV) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int m = m0 + lr + 64 * j, pix = m % (H * W);
-      py[j] = pix / W;
-      px[j] = pix - py[j] * W;
-    }
-  }
-  auto gload = [&](int s, int k0) {
-    int tap = 0, dy = 0, dx = 0, kc = k0 + lk;
-    if (CONV) { tap = (k0 + lk) / lda; kc = (k0 + lk) - tap * lda; dy = tap / 3 - 1; dx = tap - (tap / 3) * 3 - 1; }   // lda = Ci
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int r = lr + 64 * j, k = k0 + lk;
-      if (CONV) {
-        const int yy = py[j] + dy, xx = px[j] + dx;
-        const bool ok = m0 + r < M && k < K && yy >= 0 && yy < H && xx >= 0 && xx < W;
-        ra[s][j] = ok ? *reinterpret_cast<const float4 *>(A + ((int64_t)(m0 + r) + dy * W + dx) * lda + kc) : make_float4(0, 0, 0, 0);
-      } else {
-        ra[s][j] = (m0 + r < M && k < K) ? *reinterpret_cast<const float4 *>(A + (int64_t)(m0 + r) * lda + k) : make_float4(0, 0, 0, 0);
-      }
-      rb[s][j] = (n0 + r < N && k < K) ? *reinterpret_cast<const float4 *>(B + (int64_t)(n0 + r) * ldb + k) : make_float4(0, 0, 0, 0);
-    }
-  };
-  // split + store one staged float4 (operand 0 = A, 1 = B; j = which of the thread's two rows) of register stage s into LDS
-  // stage buf.  Issued in four pieces BETWEEN the MFMA groups of a step: the matrix pipe works ~128 cycles on a group of
-  // four, the ~25 VALU operations of a piece run in that shadow.
-  auto lstore1 = [&](int s, int buf, int op, int j) {
-    const float4 v = op == 0 ? ra[s][j] : rb[s][j];
-    Split4 x;
-    if (ABL == 3) { x.hi = make_uint2(pk_bf16(v.x, v.y), pk_bf16(v.z, v.w)); x.mid = x.lo = make_uint2(0, 0); }
-    else x = split4(v);
-    const int r = lr + 64 * j;
-    bf16_t(*P)[BM][PITCH] = op == 0 ? As[buf] : Bs[buf];
-    *reinterpret_cast<uint2 *>(&P[0][r][lk]) = x.hi; *reinterpret_cast<uint2 *>(&P[1][r][lk]) = x.mid; *reinterpret_cast<uint2 *>(&P[2][r][lk]) = x.lo;
-  };
-  auto lstore = [&](int s, int buf) { lstore1(s, buf, 0, 0); lstore1(s, buf, 0, 1); lstore1(s, buf, 1, 0); lstore1(s, buf, 1, 1); };
-  // two-level accumulation: `acc` collects FLUSH k-steps (256 contraction elements), then is added to `tot` and cleared — the
-  // rounding error of a long contraction (K = 2304 in the 3 x 3 convolution) grows with the square root of the chain length
-  constexpr int FLUSH = 16;
-  f32x16 acc[2][2], tot[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) { acc[i][j][e] = 0.f; tot[i][j][e] = 0.f; }
-
-  const int KT = (K + BK - 1) / BK;
-  gload(0, 0);
-  if (KT > 1) gload(1, BK);
-  lstore(0, 0);
-  __syncthreads();
-  const int fr = lane & 31, fk = (lane >> 5) * 8;
-  // step kt computes from LDS stage kt & 1, writes tile kt + 1 (register stage (kt + 1) & 1, loaded during step kt - 1) to the
-  // other LDS stage and issues the loads of tile kt + 2 into the register stage it has just freed
-  auto step = [&](int kt, int par) {
-    if (kt + 2 < KT) gload(par, (kt + 2) * BK);        // first thing in the step: a whole step of latency cover (see the wide kernel)
-    hwbf16x8 a[3][2], b[3][2];
-#pragma unroll
-    for (int p = 0; p < 3; ++p)
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        a[p][i] = frag(&As[par][p][wm + i * 32 + fr][fk]);
-        b[p][i] = frag(&Bs[par][p][wn + i * 32 + fr][fk]);
-      }
-    // one partial product at a time over the four accumulators (consecutive MFMAs independent); smallest terms first
-#define TERM(PA, PB)                                                         \
-  _Pragma("unroll") for (int i = 0; i < 2; ++i)                              \
-      _Pragma("unroll") for (int j = 0; j < 2; ++j) mma16k(acc[i][j], a[PA][i], b[PB][j]);
-    const bool more = kt + 1 < KT;
-    if (ABL != 1 && ABL != 2) {
-      TERM(2, 0) if (more) lstore1(par ^ 1, par ^ 1, 0, 0);
-      TERM(0, 2) if (more) lstore1(par ^ 1, par ^ 1, 0, 1);
-      TERM(1, 1) if (more) lstore1(par ^ 1, par ^ 1, 1, 0);
-      TERM(1, 0) if (more) lstore1(par ^ 1, par ^ 1, 1, 1);
-      TERM(0, 1)
-    } else if (more) lstore(par ^ 1, par ^ 1);
-    if (ABL != 1) { TERM(0, 0) }
-#undef TERM
-    if (ABL == 1) acc[0][0][0] += (float)a[0][0][0] + (float)b[2][1][1] + (float)a[1][1][2] + (float)b[1][0][3] + (float)a[2][0][5] + (float)b[0][0][7];
-    if (KT > FLUSH && (kt + 1) % FLUSH == 0) {
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) { tot[i][j][e] += acc[i][j][e]; acc[i][j][e] = 0.f; }
-    }
-    __syncthreads();
-  };
-  for (int kt = 0; kt < KT; kt += 2) {
-    step(kt, 0);
-    if (kt + 1 < KT) step(kt + 1, 1);
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] += tot[i][j][e];
-  // C layout of the 32x32 MFMA: col = lane & 31 (B row), row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5) (A row); bias loaded before the
-  // first store and a branch-free path for interior tiles (see the wide kernel's epilogue: guarded stores serialise on vmcnt(0))
-  float bv[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int col = n0 + wn + j * 32 + (lane & 31);
-    bv[j] = (bias && col < N) ? bias[col] : 0.f;
-  }
-  const bool full = m0 + BM <= M && n0 + BN <= N;
-  auto store_tile = [&](auto guard) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int col = n0 + wn + j * 32 + (lane & 31);
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int row = m0 + wm + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-          float v = acc[i][j][e] + bv[j];
-          if (RELU) v = fmaxf(v, 0.f);
-          if ((!decltype(guard)::value || (row < M && col < N)) && (ABL != 4 || v_never(acc[i][j][e]))) C[(int64_t)row * ldc + col] = v;
-        }
-    }
-  };
-  if (full) store_tile(std::false_type{});
-  else store_tile(std::true_type{});
-}
-
-// ---------------------------------------------------------------------------------------------- wide tiles
-// The 128 x 128 kernel above is bound by the L2 -> LDS operand stream, not by the matrix pipe: every A element is fetched
-// N / 128 times and every B element M / 128 times — 4 M N K (1/BM + 1/BN) bytes, 704 MB for the encoder's 1024 <- 256 Linear at
-// M = 43 008, which the kernel moves in ~100 us with the MFMAs switched off (x3_ablate 1), against 54 us of matrix work.
-// 256 x 256 tiles halve that stream (352 MB): 8 wavefronts (4 x 2), each 64 x 128 of the tile = 2 x 4 MFMA tiles (128
-// accumulator registers), one workgroup per CU, two 120 KB LDS stages of three bf16 planes.  Per 16-wide step a wave issues
-// 48 MFMAs (1 536 cycles) against 18 operand fragments; the B fragments are fetched for two column tiles at a time so that
-// 12 fragments, not 18, are live next to the accumulators.
-// Measured (with the schedule of the step below): 161-169 vs 202-216 us on the 1024 <- 256 Linear, 143 vs 167 on 256 <- 1024, a tie
-// at K = 256 with N = 256 / 512.  Ablations of THIS kernel on that shape: no MFMA
-// 117 us, no output stores 129, no operand split 148 — operand staging (~42) + split (28) + matrix work (59, the full bf16
-// rate) + stores (47, 3.7 TB/s) simply ADD UP: one barrier per 16-wide step keeps the 8 wavefronts in lock-step, so the pipes
-// take turns instead of overlapping.  A 128 x 256 variant with two independent workgroups per CU (template parameter WVM = 2,
-// `x3_narrow` 3) measures the same (172 vs 169 us) — so it is not the common barrier; moving the global loads to the top of
-// the step and a conflict-free LDS layout changed nothing either; the guide's register-staging order (write tile t + 1 right
-// after the barrier, re-issue the loads, then compute) is worth 6 % and frees 26 VGPRs.  What is left to try is a deeper software pipeline (fragments of step k + 1 fetched during step k, i.e.
-// three LDS stages) — the structure, not any single pipe, is the limit.
-constexpr int WBM = 256, WBN = 256;
-
-// ReLU backward of the FFN in the epilogue.  The forward (RELU) launch can leave the sign pattern of its output as a BIT per
-// element — one 32-bit word per (workgroup tile, lane, column tile j) holding that lane's 2 x 16 accumulator elements, i.e.
-// in this kernel's own C layout (`bits`, 1/32 of the tensor) — and the MASKSUM launch of the transposed product over the
-// same [M, N] (same tiling, same layout) consumes it: C = (A B^T) where the forward output was > 0, else 0, and colsum[N] +=
-// the column sums of that C (the bias gradient of the Linear in front of the ReLU).  That replaces a separate pass over the
-// [M, N] gradient (pd_relu_bwd_colsum: read 2, write 1 such tensor) by 4 words per lane.  (Reading the fp32 activations
-// themselves in the epilogue instead was measured: +140 us per launch, a net loss.)
-// WVM = wavefronts along M: 4 -> 256 x 256 tile, 512 threads, one workgroup per CU; 2 -> 128 x 256 tile, 256 threads, TWO
-// independent workgroups per CU (each SIMD then hosts one wave of each: they are not tied by a common barrier and can sit in
-// different phases of their steps).
-// BPRE: B is not fp32 but its three bf16 planes, split once per optimizer step by pd_split3_bf16 ([3][N][K], row stride K) — B
-// is a weight matrix, re-split here by every one of the M / 256 row tiles otherwise.  Bit-identical to the in-kernel split; measured
-// (tools/bench_gemm_x3_wide.py) it does NOT pay: 174.6 vs 178.6 us on 1024 <- 256, 157 vs 151 on 256 <- 1024, plus the split launch
-// — the bf16 planes are 6 bytes per element to fetch instead of 4, which costs what the saved vector work gained.  Kept as an
-// entry point (off by default in functions/encoder_core.py).
-template <bool RELU, int ABL = 0, bool MASKSUM = false, int WVM = 4, bool BPRE = false>   // ABL (tools only): 1 no MFMA, 2 no output stores, 3 no operand split
-__global__ __launch_bounds__(128 * WVM, WVM == 4 ? 1 : 2) void gemm_tn_f32x3_wide(const float *__restrict__ A, const float *__restrict__ B,
-                                                              const float *__restrict__ bias, float *__restrict__ C, int M, int N,
-                                                              int K, int lda, int ldb, int ldc, int ntiles_n,
-                                                              uint32_t *__restrict__ bits, float *__restrict__ colsum)
-{
-  // LDS tile layout: [stage][plane][k half][row][8 bf16] — a 16-wide step is two PANELS of 16-byte row slots.  An MFMA
-  // operand (8 consecutive k of row lane % 32, half lane / 32) is then ONE ds_read_b128 and the 32 lanes of a half read 512
-  // contiguous bytes (conflict-free, full LDS rate); the 40-byte row pitch of the 128 x 128 kernel needs two 8-byte reads
-  // per operand and puts rows r and r + 16 on the same banks.
-  extern __shared__ __attribute__((aligned(16))) bf16_t smem[];              // As[2][3][2][WBM][8] | Bs[2][3][2][WBN][8]
-  constexpr int TBM = 64 * WVM, NTH = 128 * WVM, RPP = NTH / 4, BPASS = WBN / RPP;     // tile rows, threads, rows per load pass, B passes
-  auto As = [&](int buf, int pl, int h, int r) -> bf16_t * { return smem + ((((buf * 3 + pl) * 2 + h) * TBM + r) << 3); };
-  auto Bs = [&](int buf, int pl, int h, int r) -> bf16_t * { return smem + 12 * TBM * 8 + ((((buf * 3 + pl) * 2 + h) * WBN + r) << 3); };
-  const int lb = xcd_chunk(blockIdx.x, gridDim.x);
-  const int m0 = (lb / ntiles_n) * TBM, n0 = (lb % ntiles_n) * WBN;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int wm = (wave >> 1) * 64, wn = (wave & 1) * 128;
-  const int lr = t >> 2, lk = (t & 3) * 4;                       // rows lr + RPP j, columns lk .. lk+3 of both tiles
-  float4 ra[2], rb[BPASS];                                       // ONE register stage (see the step)
-  uint4 rbp[3];                                                  // BPRE: one (row, k half) unit of each plane per thread (512 threads x 3 = the tile)
-  const bf16_t *Bp = reinterpret_cast<const bf16_t *>(B);
-  const int64_t PS = (int64_t)N * ldb;                           // BPRE: plane stride (ldb = K)
-  const int br = t >> 1, bh = t & 1;
-  auto gload = [&](int k0) {
-    const int k = k0 + lk;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int r = lr + RPP * j;
-      ra[j] = (m0 + r < M && k < K) ? *reinterpret_cast<const float4 *>(A + (int64_t)(m0 + r) * lda + k) : make_float4(0, 0, 0, 0);
-    }
-    if (BPRE) {
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl)
-        rbp[pl] = (n0 + br < N && k0 + bh * 8 < K) ? *reinterpret_cast<const uint4 *>(Bp + pl * PS + (int64_t)(n0 + br) * ldb + k0 + bh * 8)
-                                                   : make_uint4(0, 0, 0, 0);
-    } else {
-#pragma unroll
-      for (int j = 0; j < BPASS; ++j) {
-        const int r = lr + RPP * j;
-        rb[j] = (n0 + r < N && k < K) ? *reinterpret_cast<const float4 *>(B + (int64_t)(n0 + r) * ldb + k) : make_float4(0, 0, 0, 0);
-      }
-    }
-  };
-  auto lstore1 = [&](int buf, int op, int j) {
-    const float4 v4 = op == 0 ? ra[j] : rb[j];
-    Split4 x;
-    if (ABL == 3) { x.hi = make_uint2(pk_bf16(v4.x, v4.y), pk_bf16(v4.z, v4.w)); x.mid = x.lo = make_uint2(0, 0); }
-    else x = split4(v4);
-    const int r = lr + RPP * j;
-    bf16_t *p0 = (op == 0 ? As(buf, 0, lk >> 3, r) : Bs(buf, 0, lk >> 3, r)) + (lk & 7);
-    const int PL = 2 * (op == 0 ? TBM : WBN) * 8;                // plane stride
-    *reinterpret_cast<uint2 *>(p0) = x.hi; *reinterpret_cast<uint2 *>(p0 + PL) = x.mid; *reinterpret_cast<uint2 *>(p0 + 2 * PL) = x.lo;
-  };
-  auto lstore = [&](int buf) {
-    lstore1(buf, 0, 0); lstore1(buf, 0, 1);
-    if (BPRE) {
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<uint4 *>(Bs(buf, pl, bh, br)) = rbp[pl];
-    } else {
-#pragma unroll
-      for (int j = 0; j < BPASS; ++j) lstore1(buf, 1, j);
-    }
-  };
-  f32x16 acc[2][4];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-  const int KT = (K + BK - 1) / BK;
-  gload(0);
-  lstore(0);
-  if (KT > 1) gload(BK);
-  __syncthreads();
-  const int fr = lane & 31, fh = lane >> 5;
-  auto step = [&](int kt, int par) {
-    // the guide's register-staging schedule (T14): right after the barrier, tile kt + 1 (in the registers since the top of step
-    // kt - 1) is split and written to the other LDS buffer, the loads of tile kt + 2 are re-issued into the same registers at
-    // once (a whole step to land), and only then does the wave turn to tile kt's fragments and MFMAs — no barrier between the
-    // staging and the compute, so the waves drift apart inside a step and one's MFMAs cover another's staging
-    if (kt + 1 < KT) {
-      lstore(par ^ 1);
-      if (kt + 2 < KT) gload((kt + 2) * BK);
-    }
-    hwbf16x8 a[3][2];
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl)
-#pragma unroll
-      for (int i = 0; i < 2; ++i) a[pl][i] = *reinterpret_cast<const hwbf16x8 *>(As(par, pl, fh, wm + i * 32 + fr));
-#pragma unroll
-    for (int jp = 0; jp < 2; ++jp) {                             // two column tiles at a time
-      hwbf16x8 b[3][2];
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) b[pl][j] = *reinterpret_cast<const hwbf16x8 *>(Bs(par, pl, fh, wn + (jp * 2 + j) * 32 + fr));
-      // one partial product at a time over the four accumulators (consecutive MFMAs independent); smallest terms first
-#define WTERM(PA, PB)                                                        \
-  _Pragma("unroll") for (int i = 0; i < 2; ++i)                              \
-      _Pragma("unroll") for (int j = 0; j < 2; ++j) { if (ABL == 1) acc[i][jp * 2 + j][0] += (float)a[PA][i][0] * (float)b[PB][j][1]; else mma16k(acc[i][jp * 2 + j], a[PA][i], b[PB][j]); }
-      WTERM(2, 0)
-      WTERM(0, 2)
-      WTERM(1, 1)
-      WTERM(1, 0)
-      WTERM(0, 1)
-      WTERM(0, 0)
-#undef WTERM
-    }
-    __syncthreads();
-  };
-  for (int kt = 0; kt < KT; kt += 2) {
-    step(kt, 0);
-    if (kt + 1 < KT) step(kt + 1, 1);
-  }
-  // C layout of the 32x32 MFMA: col = lane & 31 (B row), row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5) (A row).
-  // Everything a store depends on is loaded BEFORE the first store, and interior tiles take a branch-free path: with a per-element
-  // `if (row < M)` around the store hipcc puts an s_waitcnt vmcnt(0) into every guarded block (it cannot prove the bias / bits load
-  // has been waited for on that path), and vmcnt counts stores too — every store then waited for the previous one's
-  // acknowledgement, 128 serialised round trips per wave (round 3: ~35 of this kernel's ~185 us at 1024 <- 256).
-  float bv[4];
-  uint32_t word[4];
-  int64_t widx[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int col = n0 + wn + j * 32 + (lane & 31);
-    bv[j] = (bias && col < N) ? bias[col] : 0.f;
-    widx[j] = (((int64_t)lb * (2 * WVM) + wave) * 64 + lane) * 4 + j;
-    word[j] = MASKSUM ? bits[widx[j]] : 0u;
-  }
-  const bool full = m0 + TBM <= M && n0 + WBN <= N;
-  auto store_tile = [&](auto guard) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int col = n0 + wn + j * 32 + (lane & 31);
-      float csum = 0.f;
-      uint32_t w = word[j];
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int row = m0 + wm + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-          const bool ok = !decltype(guard)::value || (row < M && col < N);
-          float v = acc[i][j][e] + bv[j];
-          if (RELU) {
-            v = fmaxf(v, 0.f);
-            if (ok) w |= (v > 0.f ? 1u : 0u) << (i * 16 + e);
-          }
-          if (MASKSUM) {
-            v = ((w >> (i * 16 + e)) & 1u) ? v : 0.f;
-            if (ok) csum += v;
-          }
-          if (ok && (ABL != 2 || v_never(acc[i][j][e]))) C[(int64_t)row * ldc + col] = v;
-        }
-      if (RELU && bits && col < N) bits[widx[j]] = w;
-      if (MASKSUM) {
-        csum += __shfl_xor(csum, 32, 64);                          // the two row halves of the wavefront hold the same column
-        if (lane < 32 && csum != 0.f && col < N) unsafeAtomicAdd(colsum + col, csum);
-      }
-    }
-  };
-  if (full) store_tile(std::false_type{});
-  else store_tile(std::true_type{});
-}
 
 // ---------------------------------------------------------------------------------------------- weight gradient
 // dW[N,K] += dY[M,N]^T X[M,K] contracts over the ROWS, so an MFMA operand (8 consecutive contraction elements per lane) is
@@ -1109,148 +749,6 @@ __global__ __launch_bounds__(256) void wgrad_tr_reduce(const float *__restrict__
 
 extern "C" void pd_dbg_set_wgrad_xcd(int v) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_wgrad_xcd), &v, sizeof(int)); }
 extern "C" void pd_dbg_set_wgrad_fast(int v) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_wgrad_fast), &v, sizeof(int)); }
-static uint32_t *const g_relu_bits = nullptr;   // plain pd_gemm_tn_f32x3 launches do not record the sign bits
-int g_pd_dbg_x3_narrow = 0;   // tools/ only (pd_debug_set "x3_narrow"): 1 = never use the 256 x 256 kernel
-int g_pd_dbg_x3 = 0;   // tools/ only (pd_debug_set "x3_ablate"): 1 no MFMA, 2 only hi*hi, 3 no operand split, 4 no output stores
-
-extern "C" int pd_gemm_tn_f32x3(const float *A, const float *B, const float *bias, float *C, int M, int N, int K, int lda,
-                                int ldb, int ldc, int relu, void *stream_)
-{
-  if (M < 0 || N < 0 || K < 0) return pd_set_error(PD_ERR_INVALID_ARG, "pd_gemm_tn_f32x3: negative size");
-  if (M == 0 || N == 0) return PD_OK;
-  if (!A || !B || !C) return pd_set_error(PD_ERR_INVALID_ARG, "pd_gemm_tn_f32x3: null pointer");
-  if ((K & 3) || (lda & 3) || (ldb & 3) || ((uintptr_t)A & 15) || ((uintptr_t)B & 15))
-    return pd_set_error(PD_ERR_INVALID_ARG, "pd_gemm_tn_f32x3: K, lda, ldb must be multiples of 4 and A, B 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream_;
-  // wide tiles where they were measured to pay (tools/bench_gemm_x3_wide.py, M = 43 008): 1024 <- 256: 161-169 vs 202-216 us; 256 <- 1024:
-  // 143 vs 167; at K = 256 with N = 256 / 512 the two kernels tie or the narrow one wins; few tiles (< 128) leave CUs idle
-  if ((!g_pd_dbg_x3 || g_pd_dbg_x3 > 10) && g_pd_dbg_x3_narrow != 1 && (N % WBN) == 0 && M >= 4 * WBM &&
-      ((int64_t)((M + WBM - 1) / WBM) * (N / WBN) >= 128 || g_pd_dbg_x3_narrow >= 2) && (N >= 1024 || K >= 512 || g_pd_dbg_x3_narrow >= 2)) {
-    const int wtn = N / WBN, wtm = (M + WBM - 1) / WBM;
-    const size_t lds = (size_t)2 * 3 * 2 * (WBM + WBN) * 8 * sizeof(bf16_t);
-    static bool attr = false;
-    if (!attr) {
-      (void)hipFuncSetAttribute((const void *)gemm_tn_f32x3_wide<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      (void)hipFuncSetAttribute((const void *)gemm_tn_f32x3_wide<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr = true;
-    }
-    if (g_pd_dbg_x3_narrow == 3) {                             // tools: 128 x 256 tiles, two workgroups per CU
-      const int htm = (M + 127) / 128;
-      const size_t hlds = (size_t)2 * 3 * 2 * (128 + WBN) * 8 * sizeof(bf16_t);
-      (void)hipFuncSetAttribute((const void *)gemm_tn_f32x3_wide<false, 0, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hlds);
-      hipLaunchKernelGGL((gemm_tn_f32x3_wide<false, 0, false, 2>), dim3((unsigned)((int64_t)htm * wtn)), dim3(256), hlds, st, A, B, bias, C, M, N, K,
-                         lda, ldb, ldc, wtn, (uint32_t *)nullptr, (float *)nullptr);
-      return pd_check_launch("pd_gemm_tn_f32x3");
-    }
-    const dim3 wg((unsigned)((int64_t)wtm * wtn)), wb(512);
-    if (g_pd_dbg_x3 > 10) {
-      auto kf = g_pd_dbg_x3 == 11 ? gemm_tn_f32x3_wide<false, 1> : g_pd_dbg_x3 == 12 ? gemm_tn_f32x3_wide<false, 2> : gemm_tn_f32x3_wide<false, 3>;
-      (void)hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(kf, wg, wb, lds, st, A, B, bias, C, M, N, K, lda, ldb, ldc, wtn, (uint32_t *)nullptr, (float *)nullptr);
-      return pd_check_launch("pd_gemm_tn_f32x3");
-    }
-    if (relu) hipLaunchKernelGGL(gemm_tn_f32x3_wide<true>, wg, wb, lds, st, A, B, bias, C, M, N, K, lda, ldb, ldc, wtn, g_relu_bits, (float *)nullptr);
-    else hipLaunchKernelGGL(gemm_tn_f32x3_wide<false>, wg, wb, lds, st, A, B, bias, C, M, N, K, lda, ldb, ldc, wtn, (uint32_t *)nullptr, (float *)nullptr);
-    return pd_check_launch("pd_gemm_tn_f32x3");
-  }
-  const int tn = (N + BN - 1) / BN, tm = (M + BM - 1) / BM;
-  const dim3 g((unsigned)((int64_t)tm * tn)), b(256);
-#define LAUNCH(R, AB) hipLaunchKernelGGL((gemm_tn_f32x3<R, AB, false>), g, b, 0, st, A, B, bias, C, M, N, K, lda, ldb, ldc, tn, 0, 0)
-  if (g_pd_dbg_x3 == 1) LAUNCH(false, 1);
-  else if (g_pd_dbg_x3 == 2) LAUNCH(false, 2);
-  else if (g_pd_dbg_x3 == 3) LAUNCH(false, 3);
-  else if (g_pd_dbg_x3 == 4) LAUNCH(false, 4);
-  else if (relu) LAUNCH(true, 0);
-  else LAUNCH(false, 0);
-#undef LAUNCH
-  return pd_check_launch("pd_gemm_tn_f32x3");
-}
-
-namespace {
-// W fp32 [N, K] (row stride ldw) -> three bf16 planes [3][R][C], (R, C) = (N, K) or, TR, (K, N) (the planes of W^T)
-template <bool TR>
-__global__ __launch_bounds__(256) void split3_planes(const float *__restrict__ W, int N, int K, int ldw, bf16_t *__restrict__ out)
-{
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x, total = (int64_t)N * K;
-  if (i >= total) return;
-  const int r = (int)(i / (TR ? N : K)), c = (int)(i - (int64_t)r * (TR ? N : K));     // output row / column
-  const float x = TR ? W[(int64_t)c * ldw + r] : W[(int64_t)r * ldw + c];
-  unsigned h, m, l;
-  split2(x, 0.f, h, m, l);
-  out[i] = (bf16_t)(h & 0xffffu); out[total + i] = (bf16_t)(m & 0xffffu); out[2 * total + i] = (bf16_t)(l & 0xffffu);
-}
-}  // namespace
-
-extern "C" int pd_split3_bf16(const float *W, int N, int K, int ldw, int transpose, void *planes, void *stream_)
-{
-  if (N <= 0 || K <= 0 || !W || !planes) return pd_set_error(PD_ERR_INVALID_ARG, "pd_split3_bf16: N=%d K=%d or null pointer", N, K);
-  const int64_t total = (int64_t)N * K;
-  const dim3 g((unsigned)((total + 255) / 256)), b(256);
-  if (transpose) hipLaunchKernelGGL(split3_planes<true>, g, b, 0, (hipStream_t)stream_, W, N, K, ldw, (bf16_t *)planes);
-  else hipLaunchKernelGGL(split3_planes<false>, g, b, 0, (hipStream_t)stream_, W, N, K, ldw, (bf16_t *)planes);
-  return pd_check_launch("pd_split3_bf16");
-}
-
-// mode 0: C = A B^T + bias; 1: relu(...) (+ sign bits when `bits`); 2: (A B^T) masked by `bits`, colsum += column sums
-extern "C" int pd_gemm_tn_f32x3_pre(const float *A, const void *Bplanes, const float *bias, float *C, uint32_t *bits, float *colsum, int M,
-                                    int N, int K, int lda, int ldc, int mode, void *stream_)
-{
-  if (M <= 0 || N <= 0 || K <= 0 || (N % WBN) || (K & 15) || M < 4 * WBM || (lda & 3) || ((uintptr_t)A & 15) || ((uintptr_t)Bplanes & 15))
-    return pd_set_error(PD_ERR_INVALID_ARG, "pd_gemm_tn_f32x3_pre: needs N %% 256 == 0, K %% 16 == 0, M >= 1024, aligned operands");
-  if (!A || !Bplanes || !C || (mode == 2 && (!bits || !colsum)) || mode < 0 || mode > 2)
-    return pd_set_error(PD_ERR_INVALID_ARG, "pd_gemm_tn_f32x3_pre: null pointer / bad mode");
-  const int wtn = N / WBN, wtm = (M + WBM - 1) / WBM;
-  const size_t lds = (size_t)2 * 3 * 2 * (WBM + WBN) * 8 * sizeof(bf16_t);
-  typedef void (*kfn)(const float *, const float *, const float *, float *, int, int, int, int, int, int, int, uint32_t *, float *);
-  const kfn k = mode == 0 ? (kfn)gemm_tn_f32x3_wide<false, 0, false, 4, true> : mode == 1 ? (kfn)gemm_tn_f32x3_wide<true, 0, false, 4, true>
-                                                                                            : (kfn)gemm_tn_f32x3_wide<false, 0, true, 4, true>;
-  static bool attr[3] = {false, false, false};
-  if (!attr[mode]) { (void)hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr[mode] = true; }
-  hipLaunchKernelGGL(k, dim3((unsigned)((int64_t)wtm * wtn)), dim3(512), lds, (hipStream_t)stream_, A, (const float *)Bplanes, bias, C, M, N, K, lda, K,
-                     ldc, wtn, bits, colsum);
-  return pd_check_launch("pd_gemm_tn_f32x3_pre");
-}
-
-extern "C" int64_t pd_gemm_tn_f32x3_relu_bits_words(int M, int N)
-{
-  if (M <= 0 || N <= 0 || (N % WBN)) return 0;
-  return (int64_t)((M + WBM - 1) / WBM) * (N / WBN) * 8 * 64 * 4;
-}
-
-extern "C" int pd_gemm_tn_f32x3_relu_bits(const float *A, const float *B, const float *bias, float *C, uint32_t *bits, int M, int N, int K,
-                                          int lda, int ldb, int ldc, void *stream_)
-{
-  if (M <= 0 || N <= 0 || (N % WBN) || M < 4 * WBM || !bits)
-    return pd_set_error(PD_ERR_INVALID_ARG, "pd_gemm_tn_f32x3_relu_bits: needs N %% 256 == 0, M >= 1024 and a bits buffer");
-  if (!A || !B || !C) return pd_set_error(PD_ERR_INVALID_ARG, "pd_gemm_tn_f32x3_relu_bits: null pointer");
-  if ((K & 3) || (lda & 3) || (ldb & 3) || ((uintptr_t)A & 15) || ((uintptr_t)B & 15))
-    return pd_set_error(PD_ERR_INVALID_ARG, "pd_gemm_tn_f32x3_relu_bits: K, lda, ldb must be multiples of 4 and A, B 16-byte aligned");
-  const int wtn = N / WBN, wtm = (M + WBM - 1) / WBM;
-  const size_t lds = (size_t)2 * 3 * 2 * (WBM + WBN) * 8 * sizeof(bf16_t);
-  static bool attr = false;
-  if (!attr) { (void)hipFuncSetAttribute((const void *)gemm_tn_f32x3_wide<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
-  hipLaunchKernelGGL(gemm_tn_f32x3_wide<true>, dim3((unsigned)((int64_t)wtm * wtn)), dim3(512), lds, (hipStream_t)stream_, A, B, bias, C, M, N, K,
-                     lda, ldb, ldc, wtn, bits, (float *)nullptr);
-  return pd_check_launch("pd_gemm_tn_f32x3_relu_bits");
-}
-
-extern "C" int pd_gemm_tn_f32x3_relumask(const float *A, const float *B, const uint32_t *bits, float *C, float *colsum, int M, int N, int K,
-                                         int lda, int ldb, int ldc, void *stream_)
-{
-  if (M < 0 || N < 0 || K < 0) return pd_set_error(PD_ERR_INVALID_ARG, "pd_gemm_tn_f32x3_relumask: negative size");
-  if (M == 0 || N == 0) return PD_OK;
-  if (!A || !B || !C || !bits || !colsum) return pd_set_error(PD_ERR_INVALID_ARG, "pd_gemm_tn_f32x3_relumask: null pointer");
-  if ((K & 3) || (lda & 3) || (ldb & 3) || ((uintptr_t)A & 15) || ((uintptr_t)B & 15) || (N % WBN) || M < 4 * WBM)
-    return pd_set_error(PD_ERR_INVALID_ARG, "pd_gemm_tn_f32x3_relumask: K, lda, ldb multiples of 4, N a multiple of 256, M >= 1024, A, B 16-byte aligned");
-  const int wtn = N / WBN, wtm = (M + WBM - 1) / WBM;
-  const size_t lds = (size_t)2 * 3 * 2 * (WBM + WBN) * 8 * sizeof(bf16_t);
-  static bool attr = false;
-  if (!attr) { (void)hipFuncSetAttribute((const void *)gemm_tn_f32x3_wide<false, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
-  hipLaunchKernelGGL((gemm_tn_f32x3_wide<false, 0, true>), dim3((unsigned)((int64_t)wtm * wtn)), dim3(512), lds, (hipStream_t)stream_, A, B,
-                     (const float *)nullptr, C, M, N, K, lda, ldb, ldc, wtn, const_cast<uint32_t *>(bits), colsum);
-  return pd_check_launch("pd_gemm_tn_f32x3_relumask");
-}
-
 int g_pd_dbg_wgrad_wide = 1;   // tools only (pd_debug_set "wgrad_wide" 0: the 128 x 128 kernel for every f16x2 weight gradient)
 // the f16x2 weight gradient takes 256 x 256 tiles when the output has several of them (measured at M = 43 008, tools/bench_wgrad_x3.py:
 // 1024 x 256 104 vs 126 us, 256 x 2304 195 vs 257; a single 256 x 256 tile LOSES, 48 vs 42 us — 256 slices of rows each leave a 256 KB
@@ -1271,15 +769,13 @@ static int wgrad_x3_launch(const float *dY, const float *X, float *dW, float *dB
   const int tk = (K + BM - 1) / BM, tn = (N + BN - 1) / BN, tiles = tk * tn;
   // the contraction is split over workgroups (each ends in a tile of atomics, or of plain stores into the workspace).  Two
   // workgroups are resident per CU, so the launch is sized to ONE round of 512: 1 044 workgroups (the old "~4 per CU" rule at
-  // 256 x 2304) ran as 3 rounds, the last one almost empty — 387 us instead of 260.  g_pd_dbg_x3 22: the old rule.
-  int splits;
-  if (g_pd_dbg_x3 == 22) { const int target = tiles <= 4 ? 256 : 1024; splits = (target + tiles - 1) / tiles; }
-  else splits = tiles >= 512 ? 1 : (512 + tiles / 2) / tiles;
+  // 256 x 2304) ran as 3 rounds, the last one almost empty — 387 us instead of 260.
+  int splits = tiles >= 512 ? 1 : (512 + tiles / 2) / tiles;
   int m_chunk = ((M + splits - 1) / splits + WS - 1) / WS * WS;
   if (m_chunk < 4 * WS) m_chunk = 4 * WS;
   splits = (M + m_chunk - 1) / m_chunk;
-  // transpose-read form when the operands allow 16-byte row loads (always, in this repo); x3_ablate 21 forces the scalar-staged one
-  const bool vec = !(N & 3) && !(K & 3) && !(ldy & 3) && !(ldx & 3) && !((uintptr_t)dY & 15) && !((uintptr_t)X & 15) && g_pd_dbg_x3 != 21;
+  // transpose-read form when the operands allow 16-byte row loads (always, in this repo)
+  const bool vec = !(N & 3) && !(K & 3) && !(ldy & 3) && !(ldx & 3) && !((uintptr_t)dY & 15) && !((uintptr_t)X & 15);
   if (convH && !vec) return pd_set_error(PD_ERR_INVALID_ARG, "%s: channel counts must be multiples of 4 and the tensors 16-byte aligned", who);
   if (h2 && !vec) return pd_set_error(PD_ERR_INVALID_ARG, "%s: N, K, ldy, ldx must be multiples of 4 and dY, X 16-byte aligned", who);
   if (!vec) {
@@ -1309,9 +805,9 @@ static int wgrad_x3_launch(const float *dY, const float *X, float *dW, float *dB
     if (ws) hipLaunchKernelGGL(wgrad_h2w_reduce, dim3((unsigned)(wtiles * 128), wgroups), dim3(WNT), 0, st, (const float *)ws, dW, N, K, ldw, wtk, wtiles, wsplits);
     return pd_check_launch(who);
   }
-  if (ws && (ws_floats < (int64_t)tiles * splits * BN * BM || splits < 2 || g_pd_dbg_x3 == 25)) ws = nullptr;   // not worth / does not fit: atomics
+  if (ws && (ws_floats < (int64_t)tiles * splits * BN * BM || splits < 2)) ws = nullptr;   // not worth / does not fit: atomics
   auto kfn = h2 ? (convH ? gemm_wgrad_f32x3_tr<0, true, true> : gemm_wgrad_f32x3_tr<0, false, true>)
-                 : convH ? gemm_wgrad_f32x3_tr<0, true> : g_pd_dbg_x3 == 24 ? gemm_wgrad_f32x3_tr<2, false> : gemm_wgrad_f32x3_tr<0, false>;
+                 : gemm_wgrad_f32x3_tr<0, false>;                 // (a convolution always comes in the two-plane form)
   hipLaunchKernelGGL(kfn, dim3((unsigned)(tiles * splits)), dim3(256), 0, st, dY, X, dW, dB, ws, M, N, K, ldy, ldx, ldw, tk, tiles, m_chunk,
                      convH, convW, y_amax, x_amax);
   const int groups = tiles * 64 >= 2048 ? 1 : splits >= 64 ? 8 : splits >= 16 ? 4 : 1;
@@ -1468,31 +964,3 @@ extern "C" int pd_gemm_wgrad_acc_f32x3_ws(const float *dY, const float *X, float
 {
   return wgrad_x3_launch(dY, X, dW, dB, workspace, workspace_floats, M, N, K, ldy, ldx, ldw, (hipStream_t)stream_, "pd_gemm_wgrad_acc_f32x3_ws");
 }
-
-extern "C" int pd_conv3x3_wgrad_nhwc_f32x3(const float *dY, const float *X, float *dWk, float *dB, float *workspace, int64_t workspace_floats,
-                                           int B, int H, int W, int Ci, int Co, void *stream_)
-{
-  if (B < 0 || H <= 0 || W <= 0 || Ci <= 0 || Co <= 0 || (Ci % BM) || (Co & 3))
-    return pd_set_error(PD_ERR_INVALID_ARG, "pd_conv3x3_wgrad_nhwc_f32x3: B=%d H=%d W=%d Ci=%d (%% 128) Co=%d (%% 4)", B, H, W, Ci, Co);
-  const int64_t M = (int64_t)B * H * W;
-  if (M > 0x7fffffffLL - 4096) return pd_set_error(PD_ERR_INVALID_ARG, "pd_conv3x3_wgrad_nhwc_f32x3: too many pixels");
-  return wgrad_x3_launch(dY, X, dWk, dB, workspace, workspace_floats, (int)M, Co, 9 * Ci, Co, Ci, 9 * Ci, (hipStream_t)stream_,
-                         "pd_conv3x3_wgrad_nhwc_f32x3", H, W);
-}
-
-extern "C" int pd_conv3x3_nhwc_f32x3(const float *X, const float *Wk, const float *bias, float *Y, int B, int H, int W, int Ci, int Co,
-                                     void *stream_)
-{
-  if (B < 0 || H <= 0 || W <= 0 || Ci <= 0 || Co <= 0 || (Ci & 15))
-    return pd_set_error(PD_ERR_INVALID_ARG, "pd_conv3x3_nhwc_f32x3: B=%d H=%d W=%d Ci=%d (%% 16) Co=%d", B, H, W, Ci, Co);
-  if (B == 0) return PD_OK;
-  if (!X || !Wk || !Y || ((uintptr_t)X & 15) || ((uintptr_t)Wk & 15))
-    return pd_set_error(PD_ERR_INVALID_ARG, "pd_conv3x3_nhwc_f32x3: null / misaligned pointer");
-  const int64_t M = (int64_t)B * H * W;
-  if (M > 0x7fffffffLL - 4096) return pd_set_error(PD_ERR_INVALID_ARG, "pd_conv3x3_nhwc_f32x3: too many pixels");
-  const int tn = (Co + BN - 1) / BN, tm = (int)((M + BM - 1) / BM);
-  hipLaunchKernelGGL((gemm_tn_f32x3<false, 0, true>), dim3((unsigned)((int64_t)tm * tn)), dim3(256), 0, (hipStream_t)stream_, X, Wk, bias, Y,
-                     (int)M, Co, 9 * Ci, Ci, 9 * Ci, Co, tn, H, W);
-  return pd_check_launch("pd_conv3x3_nhwc_f32x3");
-}
-

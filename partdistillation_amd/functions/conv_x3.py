@@ -1,15 +1,14 @@
-"""fp32 3 x 3 convolution (stride 1, pad 1) on the bf16 matrix cores with fp32-level accuracy (pd_conv3x3_nhwc_f32x3,
-include/pd_gemm.h): forward and input gradient are implicit GEMMs on the exact 3-way bf16 split of csrc/gemm_x3.hip; the weight
-gradient is the transpose-read split kernel of the encoder's weight gradients with the im2col gather in its staging.  Channels-last tensors only (the pixel decoder keeps its maps NHWC)."""
+"""fp32 3 x 3 (stride 1, pad 1) and 1 x 1 convolutions of the pixel decoder on the fp16 matrix cores with fp32-level accuracy
+(pd_conv3x3_nhwc_f16x2 / pd_conv3x3_wgrad_nhwc_f16x2 / pd_gemm_tn_f16x2, include/pd_gemm.h): two fp16 planes per operand, three
+products per term, pixels scaled by powers of two from their channel maxima.  Forward and input gradient of the 3 x 3 are implicit
+GEMMs; its weight gradient is the transpose-read kernel of the encoder's weight gradients with the im2col gather in its staging.
+Channels-last tensors only (the pixel decoder keeps its maps NHWC)."""
 import torch
 from torch.autograd import Function
 
 from .. import lib as _lib
 
 
-H2 = __import__("os").environ.get("PD_H2_CONV", "1") != "0"   # the fp16 two-plane form (pd_conv3x3_nhwc_f16x2 / pd_conv3x3_wgrad_nhwc_f16x2: three products per
-                     # term instead of six, pixels scaled by powers of two from their channel maxima); False: the 3-plane bf16 kernels
-H2_1X1 = __import__("os").environ.get("PD_H2_1X1", "1") != "0"   # ... and the 1 x 1 convolutions (forward / input gradient / filter gradient as GEMMs on the NHWC rows)
 WGRAD_X3 = True      # False: MIOpen's fp32 weight gradient (1.53 ms at 2 x 256 x 256^2, the transposed-read split kernel: see DESIGN.md)
 
 
@@ -28,20 +27,15 @@ def _pixel_amax(x):
     return am if am is not None else row_amax(x.permute(0, 2, 3, 1).reshape(-1, x.shape[1]))
 
 
-def _raw(x, wk, bias, co, x_amax=None):
-    """x channels-last [B,Ci,H,W]; wk [Co,3,3,Ci] contiguous -> channels-last [B,Co,H,W]"""
+def _raw(x, wk, bias, co, x_amax):
+    """x channels-last [B,Ci,H,W] with its pixels' channel maxima; wk [Co,3,3,Ci] contiguous -> channels-last [B,Co,H,W]"""
     B, ci, H, W = x.shape
     y = torch.empty((B, co, H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
     from .gemm import _timed_fwd, row_amax
-    if x_amax is not None:
-        w_amax = row_amax(wk.view(co, -1))
-        with _timed_fwd(2.0 * B * H * W * 9 * ci * co, "gemm_tn_f16x2<256, 256, 128, 16, 0, conv 3x3>", 4.0 * (B * H * W * (ci + co) + 9 * ci * co)):
-            _lib.check(_lib.load().pd_conv3x3_nhwc_f16x2(x.data_ptr(), wk.data_ptr(), bias.data_ptr() if bias is not None else None, y.data_ptr(),
-                                                         x_amax.data_ptr(), w_amax.data_ptr(), None, B, H, W, ci, co, _lib.current_stream()))
-        return y
-    with _timed_fwd(2.0 * B * H * W * 9 * ci * co, "gemm_tn_f32x3<conv 3x3>"):
-        _lib.check(_lib.load().pd_conv3x3_nhwc_f32x3(x.data_ptr(), wk.data_ptr(), bias.data_ptr() if bias is not None else None, y.data_ptr(),
-                                                     B, H, W, ci, co, _lib.current_stream()))
+    w_amax = row_amax(wk.view(co, -1))
+    with _timed_fwd(2.0 * B * H * W * 9 * ci * co, "gemm_tn_f16x2<256, 256, 128, 16, 0, conv 3x3>", 4.0 * (B * H * W * (ci + co) + 9 * ci * co)):
+        _lib.check(_lib.load().pd_conv3x3_nhwc_f16x2(x.data_ptr(), wk.data_ptr(), bias.data_ptr() if bias is not None else None, y.data_ptr(),
+                                                     x_amax.data_ptr(), w_amax.data_ptr(), None, B, H, W, ci, co, _lib.current_stream()))
     return y
 
 
@@ -49,10 +43,10 @@ class Conv3x3X3(Function):
     @staticmethod
     def forward(ctx, x, weight, bias):
         if not x.is_cuda:
-            raise RuntimeError("pd_conv3x3_nhwc_f32x3 runs on the GPU only (no CPU fallback in partdistillation_amd)")
+            raise RuntimeError("pd_conv3x3_nhwc_f16x2 runs on the GPU only (no CPU fallback in partdistillation_amd)")
         x = x.contiguous(memory_format=torch.channels_last)
         wk = weight.permute(0, 2, 3, 1).contiguous()                       # [Co,3,3,Ci]: free when the filter is stored channels-last
-        x_am = _pixel_amax(x) if H2 else None
+        x_am = _pixel_amax(x)
         ctx.save_for_backward(x, weight, x_am)
         ctx.has_bias = bias is not None
         return _raw(x, wk, bias, weight.shape[0], x_am)
@@ -63,7 +57,7 @@ class Conv3x3X3(Function):
         dy = dy.contiguous(memory_format=torch.channels_last)
         co, ci = weight.shape[0], weight.shape[1]
         dx = dw = db = None
-        dy_am = _pixel_amax(dy) if x_am is not None else None
+        dy_am = _pixel_amax(dy)
         if ctx.needs_input_grad[0]:
             # dX[p, ci] = sum_tap sum_co dY[p - off(tap), co] W[co, tap, ci]: the same kernel on dY with the taps flipped and the
             # filter transposed to [Ci][3][3][Co] (2.4 MB at 256 channels)
@@ -77,15 +71,10 @@ class Conv3x3X3(Function):
             B, _, H, W = x.shape
             buf = torch.zeros(co * 9 * ci + co, dtype=torch.float32, device=x.device)
             dwk, dbv = buf[:co * 9 * ci].view(co, 3, 3, ci), buf[co * 9 * ci:]
-            ws = _wgrad_workspace(x.device, int((L.pd_gemm_wgrad_f16x2_ws_floats if x_am is not None else L.pd_gemm_wgrad_f32x3_ws_floats)(co, 9 * ci)))
-            if x_am is not None:
-                _lib.check(L.pd_conv3x3_wgrad_nhwc_f16x2(dy.data_ptr(), x.data_ptr(), dwk.data_ptr(), dbv.data_ptr() if want_b else None,
-                                                         dy_am.data_ptr(), x_am.data_ptr(), ws.data_ptr() if ws is not None else None,
-                                                         ws.numel() if ws is not None else 0, B, H, W, ci, co, _lib.current_stream()))
-            else:
-                _lib.check(L.pd_conv3x3_wgrad_nhwc_f32x3(dy.data_ptr(), x.data_ptr(), dwk.data_ptr(), dbv.data_ptr() if want_b else None,
-                                                         ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0,
-                                                         B, H, W, ci, co, _lib.current_stream()))
+            ws = _wgrad_workspace(x.device, int(L.pd_gemm_wgrad_f16x2_ws_floats(co, 9 * ci)))
+            _lib.check(L.pd_conv3x3_wgrad_nhwc_f16x2(dy.data_ptr(), x.data_ptr(), dwk.data_ptr(), dbv.data_ptr() if want_b else None,
+                                                     dy_am.data_ptr(), x_am.data_ptr(), ws.data_ptr() if ws is not None else None,
+                                                     ws.numel() if ws is not None else 0, B, H, W, ci, co, _lib.current_stream()))
             dw = dwk.permute(0, 3, 1, 2) if want_w else None                # [Co,Ci,3,3] view with channels-last strides
             db = dbv if want_b else None
         elif want_w or want_b:
@@ -99,17 +88,17 @@ def conv3x3(x, weight, bias=None):
 
 
 class Conv1x1OwnWgrad(Function):
-    """fp32 1 x 1 convolution on channels-last maps = a GEMM on the NHWC rows.  H2 (default): forward, input gradient and filter /
-    bias gradient on the fp16 two-plane kernels (pd_gemm_tn_f16x2 / pd_gemm_wgrad_acc_f16x2_ws) with the pixels' channel maxima as
-    row scales (taken from functions/amax_cache when the producing kernel left them there).  Otherwise: library forward / input
-    gradient, 3-plane bf16 filter gradient.  The pixel decoder's input projections, lateral and mask-feature convolutions
+    """fp32 1 x 1 convolution on channels-last maps = a GEMM on the NHWC rows.  A channels-last map: forward, input gradient and
+    filter / bias gradient on the fp16 two-plane kernels (pd_gemm_tn_f16x2 / pd_gemm_wgrad_acc_f16x2_ws) with the pixels' channel
+    maxima as row scales (taken from functions/amax_cache when the producing kernel left them there).  Any other layout: library
+    forward / input gradient, 3-plane bf16 filter gradient.  The pixel decoder's input projections, lateral and mask-feature convolutions
     (reference msdeformattn.py:200-257)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias):
         ctx.has_bias = bias is not None
         ctx.x_bf16 = x.dtype == torch.bfloat16
-        if H2 and H2_1X1 and x.is_contiguous(memory_format=torch.channels_last):
+        if x.is_contiguous(memory_format=torch.channels_last):
             from .gemm import cast_rows_amax, gemm_tn_h2, row_amax
             B, ci, Hh, Ww = x.shape
             co = weight.shape[0]
@@ -162,7 +151,7 @@ class Conv1x1OwnWgrad(Function):
 
 
 def conv1x1_supported(x, conv):
-    return (WGRAD_X3 and x.is_cuda and (x.dtype == torch.float32 or (x.dtype == torch.bfloat16 and H2 and H2_1X1 and x.shape[1] % 8 == 0))
+    return (WGRAD_X3 and x.is_cuda and (x.dtype == torch.float32 or (x.dtype == torch.bfloat16 and x.shape[1] % 8 == 0))
             and x.dim() == 4 and conv.weight.dtype == torch.float32
             and tuple(conv.kernel_size) == (1, 1) and tuple(conv.stride) == (1, 1) and tuple(conv.padding) == (0, 0)
             and tuple(conv.dilation) == (1, 1) and conv.groups == 1 and x.shape[1] % 4 == 0 and conv.weight.shape[0] % 4 == 0

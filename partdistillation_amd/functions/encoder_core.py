@@ -9,8 +9,8 @@ ops/modules/ms_deform_attn.py:86-131.  Per layer, on the [B*S, 256] token matrix
     src = LayerNorm(src + output_proj(a))                 (pd_add_layernorm_fwd)
     src = LayerNorm(src + linear2(relu(linear1(src))))    (pd_add_layernorm_fwd, which also emits src + pos for the next layer)
 
-Forward / input-gradient GEMMs are library fp32 GEMMs (addmm / mm), weight gradients the split-K MFMA kernel
-pd_gemm_wgrad_f32; everything between them is one hand-written kernel per step instead of the 3-kernel LayerNorm
+Forward / input-gradient GEMMs run on the fp16 two-plane kernel (pd_gemm_tn_f16x2), weight gradients on the grouped two-plane /
+three-plane kernels (functions/gemm.WgradQueue); everything between them is one hand-written kernel per step instead of the 3-kernel LayerNorm
 backward, separate residual / positional adds, softmax / divide / add chains and gradient-accumulation adds that
 eager autograd issues.  All arithmetic stays fp32 like the reference (`autocast(enabled=False)`, msdeformattn.py:318).
 """
@@ -24,8 +24,7 @@ from .. import lib as _lib
 from . import rowwise as rw
 from .. import cmdbuf
 from . import gemm as _gemm
-from .gemm import (WgradQueue, gemm_tn_h2, gemm_tn_x3, gemm_tn_x3_pre, gemm_tn_x3_relu_bits, gemm_tn_x3_relumask, gemm_wgrad_acc,
-                   h2_bits_supported, pre_supported, relu_bits_supported, row_amax, split3)
+from .gemm import WgradQueue, gemm_tn_h2, gemm_wgrad_acc, h2_bits_supported, row_amax
 
 def _timed(kind, fn, *args):
     # bench.py's per-launch HIP-event hook lives next to the autograd face of the operator (imported lazily: that module
@@ -142,38 +141,10 @@ class EncoderSpec:
         self.ref, self.shapes, self.lsi = reference_points, spatial_shapes, level_start_index
 
 
-USE_X3 = True        # the FFN GEMMs (1024-wide) through pd_gemm_tn_f32x3; tools / tests switch it off to compare
 GROUP_WGRADS = os.environ.get("PD_GROUP_WGRADS", "1") != "0"  # the 5 weight gradients of every layer are queued during the backward pass and run as ONE grouped launch at its
                      # end (functions/gemm.WgradQueue -> pd_gemm_wgrad_f32x3_grouped) instead of 30 launches + 30 reduce launches
-X3_PROJ = os.environ.get("PD_X3_PROJ", "1") != "0"       # the 256-wide projections (value / offsets+weights / output and their input gradients) on the same kernel: with the
-                     # round-3 epilogue (stores no longer serialised on vmcnt(0)) 256 <- 256 at M = 43 008 runs 47.7 us against the
-                     # library's ~57 (tools/probes/gemm_planes_probe.hip); False: torch.addmm / mm (Tensile fp32)
-H2_WGRAD = os.environ.get("PD_H2_WGRAD", "1") != "0"   # ... and the weight gradients (pd_gemm_wgrad_f16x2_grouped: slab-wise scales)
-H2 = os.environ.get("PD_H2", "1") != "0"   # forward / input-gradient GEMMs on the fp16 two-plane kernel (pd_gemm_tn_f16x2: 3 products per term instead of 6, operand rows
-                     # scaled by powers of two from their absolute maxima, which the LayerNorm kernels and the GEMM epilogues emit as they write the
-                     # rows): 1024 <- 256 at M = 43 008 96 us vs 132 (x3), 256 <- 1024 85 vs 132, 256 <- 256 29 vs 44 (tools/bench_gemm_h2.py)
-PRESPLIT = False     # weight operand split into its bf16 planes once per use (pd_split3_bf16 + pd_gemm_tn_f32x3_pre).  Bit-identical results;
-                     # measured 174.6 vs 178.6 us (1024 <- 256) and 157 vs 151 us (256 <- 1024) plus 8 us per split launch: no gain, so off
-
-
-def _proj(x, w, b=None):
-    """x [T, K] @ w [N, K]^T (+ b), fp32: a 256-wide projection of the encoder layer"""
-    if X3_PROJ and USE_X3 and x.is_cuda and x.dtype == torch.float32 and w.dtype == torch.float32 and x.shape[1] % 4 == 0 and x.stride(1) == 1 \
-            and x.stride(0) % 4 == 0:
-        return gemm_tn_x3(x, w, b)
-    return torch.addmm(b, x, w.t()) if b is not None else torch.mm(x, w.t())
-
-
-def _ffn_gemm(x, w, b=None, relu=False):
-    """x [T, K] @ w [N, K]^T (+ b) (ReLU), fp32.  The two FFN GEMMs of an encoder layer and their input gradients are the
-    large ones of the layer (22.5 GFLOP each at config 2): they run on the bf16 matrix cores with every fp32 operand split
-    exactly into three bf16 values (include/pd_gemm.h: pd_gemm_tn_f32x3, error vs fp64 at the library fp32 GEMM's level;
-    measured 174 vs 211 us and 166 vs 183 us).  The 256-wide projections stay with the library (no gain there)."""
-    if USE_X3 and x.is_cuda and x.dtype == torch.float32 and w.dtype == torch.float32 and x.shape[1] % 4 == 0:
-        return gemm_tn_x3(x, w, b, relu)
-    if relu:
-        return torch._addmm_activation(b, x, w.t(), use_gelu=False)
-    return torch.addmm(b, x, w.t()) if b is not None else torch.mm(x, w.t())
+H2_WGRAD = os.environ.get("PD_H2_WGRAD", "1") != "0"   # the weight gradients on the fp16 two-plane kernel too (pd_gemm_wgrad_f16x2_grouped: slab-wise scales)
+H2 = True            # bench.py's roofline model reads this: forward / input-gradient GEMMs are 3 products per term (the only form there is)
 
 
 _TrProblem = _lib.struct("PdTransposeProblem")
@@ -192,58 +163,24 @@ class _Stack:
 class EncoderCore(Function):
     @staticmethod
     def forward(ctx, spec: EncoderSpec, src, pos, *params):
-        ctx.set_materialize_grads(False)
+        """every GEMM of the layer sequence on pd_gemm_tn_f16x2: each operand travels with the absolute maxima of its rows (the query
+        src + pos gets them from pd_add_rows_amax_f32, LayerNorm outputs and the FFN's hidden activations from the kernel that writes
+        them).  The layer loop is a RECORDED region (cmdbuf.py): its ~60 launches are issued by one C call from the second step on."""
         B, S, C = src.shape
-        M, L, P = spec.M, spec.L, spec.P
+        if not (src.is_cuda and src.dtype == torch.float32 and pos.dtype == torch.float32 and C % 4 == 0):
+            raise RuntimeError("EncoderCore needs CUDA tensors, fp32 src and pos and C % 4 == 0 (got src " + str(src.dtype) + " on " + str(src.device)
+                               + ", pos " + str(pos.dtype) + ", C = " + str(C) + "): MSDeformAttnTransformerEncoder._fused_ok sends "
+                               "anything else down the per-layer module path")
+        ctx.set_materialize_grads(False)
         nl = len(params) // N_LAYER
         T = B * S
         src2 = src.reshape(T, C)
         src2 = src2 if src2.is_contiguous() else src2.contiguous()
         pos2 = pos.reshape(T, C)
         pos2 = pos2 if pos2.is_contiguous() else pos2.contiguous()
-        ref = spec.ref.reshape(T, L, 2)
+        ref = spec.ref.reshape(T, spec.L, 2)
         ref = ref if ref.is_contiguous() else ref.contiguous()
-        saved = []
-        x = src2
-        h2 = H2 and USE_X3 and X3_PROJ and src2.is_cuda and C % 4 == 0 and src2.dtype == torch.float32 and pos2.dtype == torch.float32
-        ctx.h2 = h2
-        if h2:                                  # (query = src + pos is formed inside, with the operands' row maxima: pd_add_rows_amax_f32)
-            return EncoderCore._forward_h2(ctx, spec, src2, pos2, None, ref, params, (B, S, C, nl))
-        q = src2 + pos2
-        for i in range(nl):
-            (so_w, so_b, aw_w, aw_b, vp_w, vp_b, op_w, op_b, n1_w, n1_b, l1_w, l1_b, l2_w, l2_b, n2_w, n2_b) = params[i * N_LAYER:(i + 1) * N_LAYER]
-            value = _proj(x, vp_w, vp_b)
-            # sampling_offsets and attention_weights read the same input: one GEMM against their stacked weights
-            w_oa, b_oa = torch.cat([so_w, aw_w]), torch.cat([so_b, aw_b])
-            oa = _proj(q, w_oa, b_oa)                                                  # [T, 2MLP + MLP]
-            n_off = so_w.shape[0]
-            loc, attn = msda_prep_fwd(oa[:, :n_off], oa[:, n_off:], ref, spec.shapes, M, L, P)
-            v4, loc6, attn5 = value.view(B, S, M, C // M), loc.view(B, S, M, L, P, 2), attn.view(B, S, M, L, P)
-            a = _timed("fwd", MSDA.ms_deform_attn_forward, v4, spec.shapes, spec.lsi, loc6, attn5, spec.im2col_step).view(T, C)
-            z1, y1, _, _, m1, r1 = rw.add_ln_fwd(_proj(a, op_w, op_b), x, n1_w, n1_b, spec.eps)
-            hbits = None
-            pre = USE_X3 and PRESPLIT and pre_supported(T, l1_w.shape[0], l1_w.shape[1]) and pre_supported(T, l2_w.shape[0], l2_w.shape[1])
-            if pre:                       # weights split into their bf16 planes once here, not by every row tile of the GEMMs
-                h, hbits = gemm_tn_x3_pre(y1, split3(l1_w), l1_b, mode=1, want_bits=True)
-            elif USE_X3 and relu_bits_supported(T, l1_w.shape[0]):
-                h, hbits = gemm_tn_x3_relu_bits(y1, l1_w, l1_b)                       # + the sign bits the backward's epilogue consumes
-            else:
-                h = _ffn_gemm(y1, l1_w, l1_b, relu=True)                             # bias + ReLU in the GEMM epilogue
-            ffn2 = gemm_tn_x3_pre(h, split3(l2_w), l2_b) if pre else _ffn_gemm(h, l2_w, l2_b)
-            last = i == nl - 1
-            z2, y2, _, ypos, m2, r2 = rw.add_ln_fwd(ffn2, y1, n2_w, n2_b, spec.eps, c_dtype=torch.float32,
-                                                    pos=pos2, pos_div=1, want_ypos=not last)
-            saved.append((x, q, v4, loc6, attn5, a, z1, m1, r1, y1, h, z2, m2, r2, w_oa, hbits))
-            x, q = y2, ypos
-        ctx.spec, ctx.saved, ctx.params, ctx.dims = spec, saved, params, (B, S, C, nl)
-        return x.view(B, S, C)
-
-    @staticmethod
-    def _forward_h2(ctx, spec, src2, pos2, q, ref, params, dims):
-        """the same layer sequence with every GEMM on pd_gemm_tn_f16x2: each operand travels with the absolute maxima of its rows
-        (LayerNorm outputs and the FFN's hidden activations get them from the kernel that writes them).
-        The layer loop is a RECORDED region (cmdbuf.py): its ~60 launches are issued by one C call from the second step on."""
-        B, S, C, nl = dims
+        dims = (B, S, C, nl)
         P_ = lambda i, j: params[i * N_LAYER + j]
         # weights with 256 input columns of all layers in ONE matrix (rows: so, aw, vp, op, l1 per layer) + one row-maxima launch;
         # the slices of that copy are the GEMM operands (so + aw adjacent = the stacked sampling_offsets / attention_weights matrix)
@@ -252,11 +189,10 @@ class EncoderCore(Function):
         b_oa_all = torch.cat([P_(i, j) for i in range(nl) for j in (1, 3)]).view(nl, n_off + n_aw)
         l2_all = torch.cat([P_(i, 12) for i in range(nl)])                                  # [nl * C, ffn]
         ctx.wk = wk
-        use_rec = (cmdbuf.usable() and src2.is_cuda and any(ctx.needs_input_grad) and not _gemm._TIMING["on"]
-                   and not _msda_timing()["on"])
+        use_rec = (cmdbuf.usable() and any(ctx.needs_input_grad) and not _gemm._TIMING["on"] and not _msda_timing()["on"])
         if not use_rec:
             ctx.rec = None
-            x, saved, saved_am = EncoderCore._layers_h2(spec, src2, pos2, q, ref, wk, b_oa_all, l2_all, params, dims)
+            x, saved, saved_am = EncoderCore._layers_h2(spec, src2, pos2, ref, wk, b_oa_all, l2_all, params, dims)
         else:
             slots = [src2, pos2, ref, wk, b_oa_all, l2_all, spec.shapes, spec.lsi] + list(params)
             key = ("fwd", B, S, C, nl, spec.M, spec.L, spec.P, str(src2.device), _lib.current_stream())
@@ -264,18 +200,18 @@ class EncoderCore(Function):
             if rec is None or not rec.matches(slots):
                 rec = cmdbuf.Recording(slots, "encoder forward")
                 with rec:
-                    outs = EncoderCore._layers_h2(spec, src2, pos2, q, ref, wk, b_oa_all, l2_all, params, dims)
+                    outs = EncoderCore._layers_h2(spec, src2, pos2, ref, wk, b_oa_all, l2_all, params, dims)
                 x, saved, saved_am = rec.finish(outs)
                 _RECS.put(key, rec)
             else:
                 x, saved, saved_am = rec.replay(slots)
             ctx.rec, ctx.rec_gen = rec, rec.generation
         ctx.saved_am = saved_am
-        ctx.spec, ctx.saved, ctx.params, ctx.dims = spec, saved, params, (B, S, C, nl)
+        ctx.spec, ctx.saved, ctx.params, ctx.dims = spec, saved, params, dims
         return x.view(B, S, C)
 
     @staticmethod
-    def _layers_h2(spec, src2, pos2, q, ref, wk, b_oa_all, l2_all, params, dims):
+    def _layers_h2(spec, src2, pos2, ref, wk, b_oa_all, l2_all, params, dims):
         """-> (output tokens [T, C], per-layer saved tensors, per-layer saved row maxima); pd_* launches and allocations only"""
         B, S, C, nl = dims
         M, L, P = spec.M, spec.L, spec.P
@@ -283,26 +219,16 @@ class EncoderCore(Function):
         P_ = lambda i, j: params[i * N_LAYER + j]
         n_off, n_aw, n_l1 = P_(0, 0).shape[0], P_(0, 2).shape[0], P_(0, 10).shape[0]
         per = n_off + n_aw + 2 * C + n_l1
-        x_am = q_am = None
-        if q is None and src2.dtype == torch.float32 and pos2.dtype == torch.float32 and C % 4 == 0:
-            # q = src + pos, both operands' row maxima and — inside a recording — a copy of src at an arena address (the backward pass
-            # writes the addresses of layer 0's operands into the host-side table of its grouped weight-gradient launch) in ONE launch
-            q, src_c, x_am, q_am = rw.add_rows_amax(src2, pos2, copy_a=cmdbuf.active() is not None)
-            src2 = src_c if src_c is not None else src2
-        else:
-            if q is None:
-                assert cmdbuf.active() is None
-                q = src2 + pos2
-            if cmdbuf.active() is not None:
-                src2, q = rw.copy_d2d(torch.empty_like(src2), src2), rw.copy_d2d(torch.empty_like(q), q)
+        # q = src + pos, both operands' row maxima and — inside a recording — a copy of src at an arena address (the backward pass
+        # writes the addresses of layer 0's operands into the host-side table of its grouped weight-gradient launch) in ONE launch
+        q, src_c, x_am, q_am = rw.add_rows_amax(src2, pos2, copy_a=cmdbuf.active() is not None)
+        src2 = src_c if src_c is not None else src2
         wk_am = row_amax(wk)
         l2_am = row_amax(l2_all)
-        fwd_amax = C // M == 32 and L == 3 and P == 4 and src2.dtype == torch.float32       # the MSDA kernel that can emit its rows' maxima
+        fwd_amax = C // M == 32 and L == 3 and P == 4       # the MSDA kernel that can emit its rows' maxima
         zam = torch.zeros((2 * nl if fwd_amax else nl, T), dtype=torch.float32, device=src2.device)   # atomic-max targets: FFN epilogues, MSDA outputs
         h_am_all, a_am_all = zam[:nl], (zam[nl:] if fwd_amax else None)
         x = src2
-        if x_am is None:
-            x_am, q_am = row_amax(src2), row_amax(q)
         saved, saved_am = [], []
         for i in range(nl):
             (so_w, so_b, aw_w, aw_b, vp_w, vp_b, op_w, op_b, n1_w, n1_b, l1_w, l1_b, l2_w, l2_b, n2_w, n2_b) = params[i * N_LAYER:(i + 1) * N_LAYER]
@@ -366,7 +292,7 @@ class EncoderCore(Function):
 
     @staticmethod
     def _stacks_t_one_launch(params, nl, wk, n_oa, per, C):
-        """the five transposed weight stacks of _backward_h2 (linear1, linear2, output_proj, value_proj of every layer from the flat
+        """the five transposed weight stacks of backward (linear1, linear2, output_proj, value_proj of every layer from the flat
         parameter buffer, and the stacked sampling_offsets + attention_weights rows of `wk`) by ONE pd_transpose_batched_f32 launch into one
         buffer — or None when the layers' weights do not sit at one spacing (then the per-stack ATen copies run)"""
         import ctypes
@@ -400,12 +326,15 @@ class EncoderCore(Function):
         return views
 
     @staticmethod
-    def _backward_h2(ctx, d_out):
-        """backward of _forward_h2: an eager prologue (the transposed weight stacks: ATen copies), the layer loop as a recorded region
+    def backward(ctx, d_out):
+        """an eager prologue (the transposed weight stacks: ATen copies), the layer loop as a recorded region
         (~110 launches incl. the grouped weight gradients: one C call from the second step on), three elementwise sums at the end"""
         spec, params = ctx.spec, ctx.params
         B, S, C, nl = ctx.dims
         T = B * S
+        # frozen encoder (FREEZE_KEYS contains "encoder", the shipped scripts' setting: base_trainer.py:97-100): none of its
+        # parameters requires a gradient, so the five weight-gradient GEMMs per layer (a third of the encoder's backward
+        # FLOPs) are skipped; the input gradient still flows (input_proj / level_embed in front of it stay trainable)
         need_w = any(ctx.needs_input_grad[3:])
         n_off, n_aw, n_l1 = params[0].shape[0], params[2].shape[0], params[10].shape[0]
         per = n_off + n_aw + 2 * C + n_l1
@@ -422,7 +351,7 @@ class EncoderCore(Function):
         stacks = (l1_t, l2_t, op_t, vp_t, oa_t)
         ref = spec.ref.reshape(T, spec.L, 2)                       # (the fused MSDA backward re-forms the sampling locations from it)
         ref = ref if ref.is_contiguous() else ref.contiguous()
-        rec_f = getattr(ctx, "rec", None)
+        rec_f = ctx.rec
         if rec_f is None:
             dy, dy2, dyq, d_pos, grads = EncoderCore._bwd_layers_h2(spec, params, ctx.dims, ctx.saved, ctx.saved_am, dy, stacks, need_w, ref)
         else:
@@ -552,158 +481,3 @@ class EncoderCore(Function):
         if queue is not None:
             queue.flush()
         return dy, dy2, dyq, d_pos, grads
-
-    @staticmethod
-    def backward(ctx, d_out):
-        if getattr(ctx, "h2", False) and X3_PROJ and USE_X3:
-            return EncoderCore._backward_h2(ctx, d_out)
-        spec, params = ctx.spec, ctx.params
-        B, S, C, nl = ctx.dims
-        M, L, P = spec.M, spec.L, spec.P
-        T = B * S
-        dev = d_out.device
-        # frozen encoder (FREEZE_KEYS contains "encoder", the shipped scripts' setting: base_trainer.py:97-100): none of its
-        # parameters requires a gradient, so the five weight-gradient GEMMs per layer (a third of the encoder's backward
-        # FLOPs) are skipped; the input gradient still flows (input_proj / level_embed in front of it stay trainable)
-        need_w = any(ctx.needs_input_grad[3:])
-        from . import gemm as _gemm
-        h2 = getattr(ctx, "h2", False)
-        wh2 = h2 and H2_WGRAD
-        queue = WgradQueue(h2=wh2) if (need_w and GROUP_WGRADS and _gemm.WGRAD_X3 and d_out.is_cuda) else None
-        if not need_w:
-            wgrad = lambda *a, **k: None
-        elif queue is not None:
-            wgrad = (lambda dy_, x_, dw_, db_=None, ya=None, xa=None: queue.add(dy_, x_, dw_, db_, ya if wh2 else None, xa if wh2 else None))
-        else:
-            wgrad = (lambda dy_, x_, dw_, db_=None, ya=None, xa=None: gemm_wgrad_acc(dy_, x_, dw_, db_, h2=wh2, y_amax=ya if wh2 else None,
-                                                                                     x_amax=xa if wh2 else None))
-        # every parameter gradient of the encoder lives in ONE zero-filled fp32 buffer (a single memset): the LayerNorm /
-        # ReLU kernels and the split-K weight-gradient GEMMs all accumulate (+=) into their slices
-        offs, total = [], 0
-        for p in params:
-            offs.append(total)
-            total += (p.numel() + 3) // 4 * 4
-        n_oa = params[0].shape[0] + params[2].shape[0]                  # stacked sampling_offsets + attention_weights rows
-        oa_base, oa_per = total, n_oa * C + (n_oa + 3) // 4 * 4
-        total += nl * oa_per
-        buf = torch.zeros(total, dtype=torch.float32, device=dev)
-
-        def OA(i):
-            o = oa_base + i * oa_per
-            return buf[o:o + n_oa * C].view(n_oa, C), buf[o + n_oa * C:o + n_oa * C + n_oa]
-
-        def G(i, j):
-            p = params[i * N_LAYER + j]
-            o = offs[i * N_LAYER + j]
-            return buf[o:o + p.numel()].view(p.shape)
-        d_pos = torch.zeros((T, C), dtype=torch.float32, device=dev)
-        grads = [None] * (nl * N_LAYER)
-        # the input-gradient GEMMs want W^T row-major ([in, out] -> the "B[N, K]" operand with N = in): all layers' transposes in one
-        # stack + one copy per weight shape instead of one small launch per layer and weight
-        def T_all(j):
-            ws = [params[i * N_LAYER + j] for i in range(nl)]
-            # the layers' parameters usually sit at one spacing in a flat buffer (engine/flat_params.py, last layer first): the stack is
-            # then a strided VIEW and the transposed copy the only launch (torch.stack was a second one per weight kind, 42 us per step)
-            d = (ws[1].data_ptr() - ws[0].data_ptr()) if nl > 1 else 0
-            es = ws[0].element_size()
-            if nl > 1 and d != 0 and d % es == 0 and all(w.is_contiguous() and w.shape == ws[0].shape for w in ws) \
-                    and all(ws[i].data_ptr() - ws[0].data_ptr() == i * d for i in range(nl)) \
-                    and all(w.untyped_storage().data_ptr() == ws[0].untyped_storage().data_ptr() for w in ws):
-                N_, K_ = ws[0].shape
-                base = ws[0] if d > 0 else ws[-1]                 # lowest address first; _Stack maps the layer index back
-                return _Stack(torch.as_strided(base, (nl, N_, K_), (abs(d) // es, K_, 1)).transpose(1, 2).contiguous(), d < 0)
-            return _Stack(torch.stack(ws).transpose(1, 2).contiguous(), False)
-        l1_t, l2_t = T_all(10), T_all(12)
-        op_t, vp_t = (T_all(6), T_all(4)) if X3_PROJ and USE_X3 else (None, None)
-        oa_t = _Stack(torch.stack([sv[14] for sv in ctx.saved]).transpose(1, 2).contiguous(), False) if op_t is not None else None
-        if h2:
-            # row maxima of the transposed weights (the B operands of the input-gradient GEMMs), one launch per stack
-            t_am = lambda w: _Stack(row_amax(w.t.view(-1, w.t.shape[2])).view(nl, w.t.shape[1]), w.rev)
-            l1_tam, l2_tam, op_tam, vp_tam, oa_tam = t_am(l1_t), t_am(l2_t), t_am(op_t), t_am(vp_t), t_am(oa_t)
-            dh_am_all = torch.zeros((nl, T), dtype=torch.float32, device=dev)
-        dy = d_out.reshape(T, C)
-        dy = dy if dy.is_contiguous() else dy.contiguous()
-        dy2 = dyq = None                                       # further fp32 terms of d(src_l): via value_proj, via (src + pos)
-        for i in reversed(range(nl)):
-            (so_w, so_b, aw_w, aw_b, vp_w, vp_b, op_w, op_b, n1_w, n1_b, l1_w, l1_b, l2_w, l2_b, n2_w, n2_b) = params[i * N_LAYER:(i + 1) * N_LAYER]
-            x, q, v4, loc6, attn5, a, z1, m1, r1, y1, h, z2, m2, r2, w_oa, hbits = ctx.saved[i]
-            (g_sow, g_sob, g_aww, g_awb, g_vpw, g_vpb, g_opw, g_opb, g_n1w, g_n1b, g_l1w, g_l1b, g_l2w, g_l2b, g_n2w,
-             g_n2b) = [G(i, j) for j in range(N_LAYER)]
-            # ---- FFN + norm2
-            dz2, _, dz2_am = rw.add_ln_bwd(z2, m2, r2, n2_w, dy=dy, dy2=dy2, dypos_c=dyq, dgamma=g_n2w, dbeta=g_n2b, dbias=g_l2b,
-                                           dpos_acc=d_pos if dyq is not None else None, pos_div=1, amax=True)
-            if h2:
-                x_am, q_am, a_am, y1_am, h_am = ctx.saved_am[i]
-                wgrad(dz2, h, g_l2w, None, dz2_am, h_am)
-                if hbits is not None:
-                    dh = gemm_tn_h2(dz2, l2_t[i], None, mode=2, bits=hbits, colsum=g_l1b, a_amax=dz2_am, b_amax=l2_tam[i], c_amax=dh_am_all[i])
-                    dh_am = dh_am_all[i]
-                else:
-                    dh = rw.relu_bwd_colsum(gemm_tn_h2(dz2, l2_t[i], a_amax=dz2_am, b_amax=l2_tam[i]), h, g_l1b)
-                    dh_am = row_amax(dh)
-                wgrad(dh, y1, g_l1w, None, dh_am, y1_am)
-                dy1 = gemm_tn_h2(dh, l1_t[i], a_amax=dh_am, b_amax=l1_tam[i])
-                del dh
-                dz1, _, dz1_am = rw.add_ln_bwd(z1, m1, r1, n1_w, dy=dz2, dy2=dy1, dgamma=g_n1w, dbeta=g_n1b, dbias=g_opb,
-                                               out=None if queue is not None else dz2, amax=True)
-                wgrad(dz1, a, g_opw, None, dz1_am, a_am)
-                da = gemm_tn_h2(dz1, op_t[i], a_amax=dz1_am, b_amax=op_tam[i]).view(B, S, C)
-                gv, gloc, gattn = _timed("bwd", MSDA.ms_deform_attn_backward, v4, spec.shapes, spec.lsi, loc6, attn5, da, spec.im2col_step)
-                d_oa = torch.empty((T, w_oa.shape[0]), dtype=torch.float32, device=dev)
-                if prep_amax_supported(M, L, P):
-                    d_oa_am = torch.empty(T, dtype=torch.float32, device=dev)
-                    msda_prep_bwd(gloc, gattn, attn5, spec.shapes, T, M, L, P, out=d_oa, amax=d_oa_am)
-                else:
-                    msda_prep_bwd(gloc, gattn, attn5, spec.shapes, T, M, L, P, out=d_oa)
-                    d_oa_am = row_amax(d_oa)
-                g_oaw, g_oab = OA(i)
-                wgrad(d_oa, q, g_oaw, g_oab, d_oa_am, q_am)                   # both weight gradients in one split-K GEMM
-                n_off = so_w.shape[0]
-                g_sow, g_aww, g_sob, g_awb = g_oaw[:n_off], g_oaw[n_off:], g_oab[:n_off], g_oab[n_off:]
-                dq = gemm_tn_h2(d_oa, oa_t[i], a_amax=d_oa_am, b_amax=oa_tam[i])
-                gv2 = gv.view(T, C)
-                gv_am = row_amax(gv2)
-                wgrad(gv2, x, g_vpw, g_vpb, gv_am, x_am)
-                dxv = gemm_tn_h2(gv2, vp_t[i], a_amax=gv_am, b_amax=vp_tam[i])
-                grads[i * N_LAYER:(i + 1) * N_LAYER] = [g_sow, g_sob, g_aww, g_awb, g_vpw, g_vpb, g_opw, g_opb, g_n1w, g_n1b,
-                                                         g_l1w, g_l1b, g_l2w, g_l2b, g_n2w, g_n2b]
-                dy, dy2, dyq = dz1, dxv, dq
-                continue
-            wgrad(dz2, h, g_l2w)
-            pre = hbits is not None and USE_X3 and PRESPLIT and pre_supported(T, l2_w.shape[1], l2_w.shape[0]) and pre_supported(T, l1_w.shape[1], l1_w.shape[0])
-            if pre:
-                dh = gemm_tn_x3_pre(dz2, split3(l2_w, transpose=True), mode=2, bits=hbits, colsum=g_l1b)
-            elif hbits is not None:
-                dh = gemm_tn_x3_relumask(dz2, l2_t[i], hbits, g_l1b)                # ReLU backward + bias gradient in the epilogue
-            else:
-                dh = rw.relu_bwd_colsum(_ffn_gemm(dz2, l2_t[i]), h, g_l1b)
-            wgrad(dh, y1, g_l1w)
-            dy1 = gemm_tn_x3_pre(dh, split3(l1_w, transpose=True)) if pre else _ffn_gemm(dh, l1_t[i])
-            del dh
-            # ---- deformable attention + norm1
-            # (with queued weight gradients dz2 stays alive until the grouped launch: dz1 gets its own buffer)
-            dz1, _ = rw.add_ln_bwd(z1, m1, r1, n1_w, dy=dz2, dy2=dy1, dgamma=g_n1w, dbeta=g_n1b, dbias=g_opb, out=None if queue is not None else dz2)
-            wgrad(dz1, a, g_opw)
-            da = (_proj(dz1, op_t[i]) if op_t is not None else torch.mm(dz1, op_w)).view(B, S, C)
-            gv, gloc, gattn = _timed("bwd", MSDA.ms_deform_attn_backward, v4, spec.shapes, spec.lsi, loc6, attn5, da, spec.im2col_step)
-            d_oa = torch.empty((T, w_oa.shape[0]), dtype=torch.float32, device=dev)
-            msda_prep_bwd(gloc, gattn, attn5, spec.shapes, T, M, L, P, out=d_oa)
-            g_oaw, g_oab = OA(i)
-            wgrad(d_oa, q, g_oaw, g_oab)                                  # both weight gradients in one split-K GEMM
-            n_off = so_w.shape[0]
-            g_sow, g_aww, g_sob, g_awb = g_oaw[:n_off], g_oaw[n_off:], g_oab[:n_off], g_oab[n_off:]
-            dq = _proj(d_oa, oa_t[i]) if op_t is not None else torch.mm(d_oa, w_oa)
-            gv2 = gv.view(T, C)
-            wgrad(gv2, x, g_vpw, g_vpb)
-            dxv = _proj(gv2, vp_t[i]) if vp_t is not None else torch.mm(gv2, vp_w)
-            grads[i * N_LAYER:(i + 1) * N_LAYER] = [g_sow, g_sob, g_aww, g_awb, g_vpw, g_vpb, g_opw, g_opb, g_n1w, g_n1b,
-                                                     g_l1w, g_l1b, g_l2w, g_l2b, g_n2w, g_n2b]
-            dy, dy2, dyq = dz1, dxv, dq
-        if queue is not None:
-            queue.flush()
-        d_pos += dyq
-        d_src = dy + dy2
-        d_src += dyq
-        if not need_w:
-            grads = [None] * len(grads)
-        return (None, d_src.view(B, S, C), d_pos.view(B, S, C), *grads)

@@ -48,21 +48,6 @@ class _timed_fwd:
             _TIMING["fwd"].append((self.a, self.b, (self.flops, self.label, self.nbytes)))
 
 
-def gemm_tn_x3(a, b, bias=None, relu=False):
-    """a [M,K], b [N,K] fp32 -> a @ b.T (+bias) (ReLU) with fp32-level accuracy on the bf16 matrix cores
-    (pd_gemm_tn_f32x3: exact 3-way bf16 split of every operand, 6 partial products, fp32 accumulation)."""
-    if not a.is_cuda:
-        raise RuntimeError("pd_gemm_tn_f32x3 runs on the GPU only (no CPU fallback in partdistillation_amd)")
-    assert a.dtype == torch.float32 and b.dtype == torch.float32 and a.stride(1) == 1 and b.stride(1) == 1
-    M, K = a.shape
-    N = b.shape[0]
-    c = torch.empty((M, N), dtype=torch.float32, device=a.device)
-    with _timed_fwd(2.0 * M * N * K, "gemm_tn_f32x3(_wide)"):
-        _lib.check(_lib.load().pd_gemm_tn_f32x3(a.data_ptr(), b.data_ptr(), bias.data_ptr() if bias is not None else None, c.data_ptr(),
-                                                M, N, K, a.stride(0), b.stride(0), N, int(relu), _stream()))
-    return c
-
-
 def row_amax(x):
     """absolute row maxima of an fp32 matrix (pd_row_amax_f32): the scaling input of gemm_tn_h2 for an operand whose producer
     does not emit them"""
@@ -131,69 +116,6 @@ def gemm_tn_h2(a, b, bias=None, mode=0, bits=None, colsum=None, a_amax=None, b_a
     with _timed_fwd(2.0 * M * N * K, label, 4.0 * (M * K + N * K + M * N)):
         _lib.check(L.pd_gemm_tn_f16x2(*args))
     return (c, bits) if (mode == 1 and want_bits) else c
-
-
-def split3(w, transpose=False):
-    """fp32 weight [N,K] -> its three bf16 planes [3,N,K] (or [3,K,N] of w.T): pd_split3_bf16, once per step per weight."""
-    assert w.is_cuda and w.dtype == torch.float32 and w.dim() == 2 and w.stride(1) == 1
-    N, K = w.shape
-    out = torch.empty((3, K, N) if transpose else (3, N, K), dtype=torch.bfloat16, device=w.device)
-    _lib.check(_lib.load().pd_split3_bf16(w.data_ptr(), N, K, w.stride(0), int(transpose), out.data_ptr(), _stream()))
-    return out
-
-
-def pre_supported(M, N, K):
-    return N % 256 == 0 and K % 16 == 0 and M >= 1024 and (-(-M // 256)) * (N // 256) >= 128
-
-
-def gemm_tn_x3_pre(a, planes, bias=None, mode=0, bits=None, colsum=None, want_bits=False):
-    """a [M,K] fp32 @ (planes [3,N,K] of a weight).T — pd_gemm_tn_f32x3_pre.  mode 0 plain, 1 relu (want_bits: also return the sign
-    bits), 2 masked by `bits` with `colsum` += column sums."""
-    assert a.is_cuda and a.dtype == torch.float32 and a.stride(1) == 1 and planes.dtype == torch.bfloat16 and planes.is_contiguous()
-    M, K = a.shape
-    N = planes.shape[1]
-    assert planes.shape[2] == K
-    L = _lib.load()
-    c = torch.empty((M, N), dtype=torch.float32, device=a.device)
-    if mode == 1 and want_bits:
-        bits = torch.empty(int(L.pd_gemm_tn_f32x3_relu_bits_words(M, N)), dtype=torch.int32, device=a.device)
-    _lib.check(L.pd_gemm_tn_f32x3_pre(a.data_ptr(), planes.data_ptr(), bias.data_ptr() if bias is not None else None, c.data_ptr(),
-                                      bits.data_ptr() if bits is not None else None, colsum.data_ptr() if colsum is not None else None,
-                                      M, N, K, a.stride(0), N, mode, _stream()))
-    return (c, bits) if (mode == 1 and want_bits) else c
-
-
-def relu_bits_supported(M, N):
-    return N % 256 == 0 and M >= 1024
-
-
-def gemm_tn_x3_relu_bits(a, b, bias):
-    """relu(a @ b.T + bias) and the sign bits of the result in the kernel's accumulator order (pd_gemm_tn_f32x3_relu_bits) for
-    gemm_tn_x3_relumask.  -> (c fp32 [M,N], bits int32 [words])"""
-    assert a.is_cuda and a.dtype == torch.float32 and b.dtype == torch.float32 and a.stride(1) == 1 and b.stride(1) == 1
-    M, K = a.shape
-    N = b.shape[0]
-    L = _lib.load()
-    c = torch.empty((M, N), dtype=torch.float32, device=a.device)
-    bits = torch.empty(int(L.pd_gemm_tn_f32x3_relu_bits_words(M, N)), dtype=torch.int32, device=a.device)
-    with _timed_fwd(2.0 * M * N * K, "gemm_tn_f32x3_wide<relu + sign bits>"):
-        _lib.check(L.pd_gemm_tn_f32x3_relu_bits(a.data_ptr(), b.data_ptr(), bias.data_ptr() if bias is not None else None, c.data_ptr(),
-                                                bits.data_ptr(), M, N, K, a.stride(0), b.stride(0), N, _stream()))
-    return c, bits
-
-
-def gemm_tn_x3_relumask(a, b, bits, colsum):
-    """(a @ b.T) where the recorded ReLU output was > 0, else 0 -> fp32 [M,N]; colsum[N] += its column sums
-    (pd_gemm_tn_f32x3_relumask: the FFN's ReLU backward and first-Linear bias gradient in the GEMM epilogue)."""
-    assert a.is_cuda and a.dtype == torch.float32 and b.dtype == torch.float32 and a.stride(1) == 1 and b.stride(1) == 1
-    M, K = a.shape
-    N = b.shape[0]
-    assert bits.dtype == torch.int32 and colsum.dtype == torch.float32 and colsum.numel() == N
-    c = torch.empty((M, N), dtype=torch.float32, device=a.device)
-    with _timed_fwd(2.0 * M * N * K, "gemm_tn_f32x3_wide<relu mask + column sums>"):
-        _lib.check(_lib.load().pd_gemm_tn_f32x3_relumask(a.data_ptr(), b.data_ptr(), bits.data_ptr(), c.data_ptr(), colsum.data_ptr(),
-                                                         M, N, K, a.stride(0), b.stride(0), N, _stream()))
-    return c
 
 
 # optional per-launch timing hook used by bench.py (HIP events on the launch stream; (start, stop, flops) per launch)

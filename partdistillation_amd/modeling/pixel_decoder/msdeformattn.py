@@ -92,7 +92,7 @@ class MSDeformAttnTransformerEncoder(nn.Module):
 
     def _fused_ok(self, src, pos, reference_points, padding_mask):
         if not (self.fused_core and self.num_layers and src.is_cuda and src.dtype == torch.float32 and pos is not None
-                and padding_mask is None and reference_points.shape[-1] == 2 and not torch.is_autocast_enabled("cuda")):
+                and pos.dtype == torch.float32 and padding_mask is None and reference_points.shape[-1] == 2 and not torch.is_autocast_enabled("cuda")):
             return False
         l0 = self.layers[0]
         if self.training and any(d.p > 0 for l in self.layers for d in (l.dropout1, l.dropout2, l.dropout3)):

@@ -57,7 +57,7 @@ def test_the_compiler_agrees_with_every_derived_prototype_struct_and_constant(tm
             tu.append(f'static_assert(offsetof({name}, {f}) == {d.offset} && sizeof({name}::{f}) == {d.size}, "{name}.{f}");')
     for name, v in sorted(lib._CONSTS.items()):
         tu.append(f'static_assert(({name}) == {v}, "{name}");')
-    assert len(lib.SIGNATURES) >= 212 and len(lib._STRUCTS) >= 21 and len(lib._CONSTS) >= 29
+    assert len(lib.SIGNATURES) >= 205 and len(lib._STRUCTS) >= 21 and len(lib._CONSTS) >= 29           # (213 before the eight three-plane forward entry points and queries went)
     src = tmp_path / "abi.cpp"
     src.write_text("\n".join(tu) + "\n")
     out = subprocess.run([cxx, "-x", "c++", "-std=c++17", "-fsyntax-only", "-I", lib.INCLUDE, str(src)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
@@ -151,19 +151,19 @@ def test_reader_refuses_what_it_cannot_classify(tmp_path, text, offender):
 
 
 # ---------------------------------------------------------------------------------------------- 4. sets
-# the recordable entry points (kTable of csrc/cmdbuf.hip) as of the commit that introduced the derived binding: which calls a
-# recording captures is behaviour, so a change here is a decision (tools/gen_cmdbuf_table.py), never a side effect
+# the recordable entry points (kTable of csrc/cmdbuf.hip): which calls a recording captures is behaviour, so a change here is a
+# decision (tools/gen_cmdbuf_table.py), never a side effect.  144 as of the commit that introduced the derived binding; 137 since the
+# seven three-plane forward / input-gradient entry points (GEMM, pre-split, ReLU-bit and 3 x 3 convolution forms) were retired
 RECORDABLE = """
 pd_adamw_clipped pd_adamw_clipped_shadow pd_add_layernorm_bwd pd_add_layernorm_bwd_amax pd_add_layernorm_fwd pd_add_layernorm_fwd_amax
 pd_add_rows_amax_f32 pd_affine_act_bwd2_bf16 pd_affine_act_bwd_bf16 pd_affine_act_fwd_bf16 pd_attn_bwd_d32 pd_attn_bwd_d32_ld
-pd_attn_fwd_d32 pd_attn_fwd_d32_ld pd_attn_mask_u8 pd_cast_bf16_f32_amax pd_colsum_acc pd_conv3x3_nhwc_f16x2 pd_conv3x3_nhwc_f32x3
-pd_conv3x3_wgrad_nhwc_f16x2 pd_conv3x3_wgrad_nhwc_f32x3 pd_conv_bf16_dgrad pd_conv_bf16_fwd pd_conv_bf16_wgrad pd_conv_bf16_wgrad_grouped
-pd_copy_segments pd_dec_bwd_a pd_dec_bwd_b pd_dec_fwd_a pd_dec_fwd_b pd_dec_pack_grouped pd_decoder_head_bf16 pd_filter_transpose_grouped
-pd_gemm_tn_f16x2 pd_gemm_tn_f16x2_bf16out pd_gemm_tn_f32 pd_gemm_tn_f32x3 pd_gemm_tn_f32x3_pre pd_gemm_tn_f32x3_relu_bits
-pd_gemm_tn_f32x3_relumask pd_gemm_wgrad_acc_f16x2_ws pd_gemm_wgrad_acc_f32 pd_gemm_wgrad_acc_f32x3 pd_gemm_wgrad_acc_f32x3_ws
-pd_gemm_wgrad_f16x2_grouped pd_gemm_wgrad_f32 pd_gemm_wgrad_f32x3_grouped pd_gn_coeffs_bwd pd_gn_coeffs_fwd pd_igemm_bf16 pd_igemm_bf16_seq
-pd_kmeans_assign pd_kmeans_assign_bounded pd_kmeans_assign_partial pd_kmeans_reduce pd_kmeans_reduce_update pd_kmeans_reduce_update_shift
-pd_kmeans_update pd_layernorm_rows_f32_bwd pd_layernorm_rows_f32_fwd pd_loss_vectors_bwd pd_loss_vectors_fwd pd_lsa_batched pd_mask_assign
+pd_attn_fwd_d32 pd_attn_fwd_d32_ld pd_attn_mask_u8 pd_cast_bf16_f32_amax pd_colsum_acc pd_conv3x3_nhwc_f16x2 pd_conv3x3_wgrad_nhwc_f16x2
+pd_conv_bf16_dgrad pd_conv_bf16_fwd pd_conv_bf16_wgrad pd_conv_bf16_wgrad_grouped pd_copy_segments pd_dec_bwd_a pd_dec_bwd_b pd_dec_fwd_a
+pd_dec_fwd_b pd_dec_pack_grouped pd_decoder_head_bf16 pd_filter_transpose_grouped pd_gemm_tn_f16x2 pd_gemm_tn_f16x2_bf16out pd_gemm_tn_f32
+pd_gemm_wgrad_acc_f16x2_ws pd_gemm_wgrad_acc_f32 pd_gemm_wgrad_acc_f32x3 pd_gemm_wgrad_acc_f32x3_ws pd_gemm_wgrad_f16x2_grouped
+pd_gemm_wgrad_f32 pd_gemm_wgrad_f32x3_grouped pd_gn_coeffs_bwd pd_gn_coeffs_fwd pd_igemm_bf16 pd_igemm_bf16_seq pd_kmeans_assign
+pd_kmeans_assign_bounded pd_kmeans_assign_partial pd_kmeans_reduce pd_kmeans_reduce_update pd_kmeans_reduce_update_shift pd_kmeans_update
+pd_layernorm_rows_f32_bwd pd_layernorm_rows_f32_fwd pd_loss_vectors_bwd pd_loss_vectors_fwd pd_lsa_batched pd_mask_assign
 pd_mask_point_losses_bwd pd_mask_point_losses_fwd pd_match_point_logits pd_matcher_costs pd_matcher_point_terms pd_maxpool3s2_bwd_bf16
 pd_maxpool3s2_fwd_bf16 pd_mem_prep_bwd pd_mem_prep_fwd pd_memcpy_d2d_async pd_memset_async pd_msda_backward pd_msda_forward
 pd_msda_forward_amax pd_msda_fused_backward pd_msda_fused_forward pd_msda_prep_bwd pd_msda_prep_bwd_amax pd_msda_prep_fwd
@@ -173,11 +173,11 @@ pd_point_sample_nhwc_f32 pd_point_sample_nhwc_f32_bf16 pd_point_sample_planar_bw
 pd_poly_crossings_i32 pd_relu_bwd_colsum pd_resample_cols_canvas_u8 pd_resample_rows_u8 pd_resize_bilinear_nhwc_f32
 pd_rle_sample_groups_canvas_u8 pd_rle_sample_groups_u8 pd_rle_sample_u8 pd_row_amax_f32 pd_scores_argmax_u8 pd_sgemm_nn_bf16
 pd_sgemm_nn_splitn_bf16 pd_sgemm_tn_batched_bf16 pd_sgemm_tn_bf16 pd_sgemm_tn_multi_bf16 pd_sgemm_tn_splitk_bf16 pd_sgemm_wgrad_bf16
-pd_sgemm_wgrad_grouped_bf16 pd_sgemm_wgrad_split_bf16 pd_skinny_linear_bwd pd_skinny_linear_fwd pd_split3_bf16 pd_stem7x7_fwd
-pd_stem7x7_wgrad pd_sum3_sum2_f32 pd_sumsq_accumulate pd_swin_ln_bwd pd_swin_ln_fwd pd_swin_merge_ln_bwd pd_swin_merge_ln_fwd
-pd_swin_tail_ln_bwd pd_swin_tail_ln_fwd pd_transpose_batched_f32 pd_uncertain_points pd_upsample2x_bwd_nhwc_f32
-pd_upsample_add_amax_nhwc_f32 pd_upsample_add_nhwc_f32 pd_wgrad_bf16 pd_wgrad_bf16_seq pd_window_attn_bwd_w12 pd_window_attn_bwd_w7
-pd_window_attn_fwd_w12 pd_window_attn_fwd_w7
+pd_sgemm_wgrad_grouped_bf16 pd_sgemm_wgrad_split_bf16 pd_skinny_linear_bwd pd_skinny_linear_fwd pd_stem7x7_fwd pd_stem7x7_wgrad
+pd_sum3_sum2_f32 pd_sumsq_accumulate pd_swin_ln_bwd pd_swin_ln_fwd pd_swin_merge_ln_bwd pd_swin_merge_ln_fwd pd_swin_tail_ln_bwd
+pd_swin_tail_ln_fwd pd_transpose_batched_f32 pd_uncertain_points pd_upsample2x_bwd_nhwc_f32 pd_upsample_add_amax_nhwc_f32
+pd_upsample_add_nhwc_f32 pd_wgrad_bf16 pd_wgrad_bf16_seq pd_window_attn_bwd_w12 pd_window_attn_bwd_w7 pd_window_attn_fwd_w12
+pd_window_attn_fwd_w7
 """.split()
 
 
@@ -187,7 +187,7 @@ def test_exported_declared_and_recordable_sets():
     exported = {ln.split()[2] for ln in out.splitlines() if len(ln.split()) == 3 and ln.split()[1] in "TW" and ln.split()[2].startswith("pd_")}
     assert exported == set(lib.SIGNATURES), (sorted(exported - set(lib.SIGNATURES)), sorted(set(lib.SIGNATURES) - exported))
     so = lib.load()
-    assert len(RECORDABLE) == len(set(RECORDABLE)) == 144
+    assert len(RECORDABLE) == len(set(RECORDABLE)) == 137
     recordable = {n for n in lib.SIGNATURES if so.pd_cmd_fn_index(n.encode()) >= 0}
     assert recordable == set(RECORDABLE), (sorted(recordable - set(RECORDABLE)), sorted(set(RECORDABLE) - recordable))
     for n in RECORDABLE:                                             # Thunk<&f>::nargs, from the real prototype, against the derived argtypes

@@ -301,6 +301,35 @@ def test_fused_encoder_core_matches_module_path():
         assert err < (2e-2 if g2[k].dim() == 4 else 2e-3), (k, err)
 
 
+def test_fused_encoder_core_refuses_a_pos_that_is_not_fp32(monkeypatch):
+    """the fused core has one implementation (fp32 src and pos on the two-plane GEMMs): the encoder sends an fp64 `pos` down the
+    per-layer module path, and a direct EncoderCore.apply with it raises before it launches or allocates anything"""
+    from partdistillation_amd import lib
+    from partdistillation_amd.functions.encoder_core import EncoderCore, EncoderSpec
+    from partdistillation_amd.modeling.pixel_decoder.msdeformattn import MSDeformAttnTransformerEncoder, MSDeformAttnTransformerEncoderLayer
+    enc = MSDeformAttnTransformerEncoder(lambda: MSDeformAttnTransformerEncoderLayer(256, 512, 0.0, "relu", 3, 8, 4), 2).to(DEV)
+    sizes = [(12, 16), (6, 8), (3, 4)]
+    shapes = torch.as_tensor(sizes, dtype=torch.long, device=DEV)
+    lsi = torch.cat((shapes.new_zeros((1,)), shapes.prod(1).cumsum(0)[:-1]))
+    S = sum(h * w for h, w in sizes)
+    src, pos = _r((2, S, 256), 960).requires_grad_(), _r((2, S, 256), 961)
+    ref = enc.get_reference_points(sizes, torch.ones((2, 3, 2), device=DEV), DEV)
+    assert enc._fused_ok(src, pos, ref, None)
+    assert not enc._fused_ok(src, pos.double(), ref, None)
+    l0 = enc.layers[0]
+    spec = EncoderSpec(l0.self_attn.n_heads, l0.self_attn.n_levels, l0.self_attn.n_points, l0.norm1.eps, l0.self_attn.im2col_step, ref, shapes, lsi)
+    params, pos64 = enc._core_params(), pos.double()
+    torch.cuda.synchronize()
+
+    def no_launch():
+        raise AssertionError("EncoderCore reached the library before it checked its inputs")
+    monkeypatch.setattr(lib, "load", no_launch)
+    before = torch.cuda.memory_stats()["allocation.all.allocated"]
+    with pytest.raises(RuntimeError, match="fp32 src and pos"):
+        EncoderCore.apply(spec, src, pos64, *params)
+    assert torch.cuda.memory_stats()["allocation.all.allocated"] == before
+
+
 # ----------------------------------------------------------------------------- point sampling + sparse-mask criterion
 @pytest.mark.parametrize("B,C,H,W,P", [(2, 256, 64, 48, 1000), (1, 8, 5, 7, 33)])
 def test_point_sample_nhwc_vs_grid_sample(B, C, H, W, P):

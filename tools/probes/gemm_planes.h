@@ -4,7 +4,7 @@
 // global load -> registers -> ~25 VALU operations per float4 -> three ds_write_b64 — and its ablations show that staging and
 // split are paid on top of the matrix time (the pipes take turns).  Here the operands arrive ALREADY split, as three bf16
 // planes [3][rows][cols] written once by whoever produced the tensor (a LayerNorm / ReLU / sampling epilogue, or
-// pd_split3_rows), and a tile is staged by direct-to-LDS loads (global_load_lds_dwordx4: no VGPRs, no VALU, no ds_write) into
+// a separate split pass), and a tile is staged by direct-to-LDS loads (global_load_lds_dwordx4: no VGPRs, no VALU, no ds_write) into
 // an NS-stage ring with counted vmcnt waits across raw barriers, so the only per-step vector work left is 18 ds_read_b128 for
 // 48 MFMAs.  Six of the nine partial products are accumulated in fp32, smallest first (see gemm_x3.hip for the error bound).
 //
@@ -50,7 +50,7 @@ __device__ __forceinline__ void split2(float x0, float x1, unsigned &h, unsigned
 // back, 32 bytes each.  A GEMM stage wants, per operand row, the 16 contraction elements of one chunk: with row-major planes
 // that is 32 bytes out of every 128-byte line (the L2 -> L1 path then carries 4x the useful bytes: measured 14 B/clk/CU, the
 // whole kernel bound by it); in panel layout the 32 rows one DMA instruction stages are ONE contiguous kilobyte.
-__global__ __launch_bounds__(256) void split3_panels(const float *__restrict__ x, int ld, bf16_t *__restrict__ out, int R, int C)
+__global__ __launch_bounds__(256) void split_planes_panels(const float *__restrict__ x, int ld, bf16_t *__restrict__ out, int R, int C)
 {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;      // (row, 4-column group)
   const int cg = C >> 2;

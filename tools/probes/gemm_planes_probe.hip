@@ -4,8 +4,8 @@
 //   tn    : C[M,N]  = A[M,K] . B[N,K]^T          (Linear forward / input gradient; contraction along the rows' memory order)
 //   wgrad : dW[N,K] = dY[M,N]^T . X[M,K]         (contraction over the rows: ds_read_b64_tr_b16 transposes on the way out of LDS)
 // Build + run (GPU box):  hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/probes/gemm_planes_probe.hip -o gpurun_out/gpp -ldl && gpurun_out/gpp
-// It checks every variant against an fp64 host reference on sampled rows and times it next to the library's in-kernel-split
-// kernels (dlopen of partdistillation_amd/libpd_hip.so when present).
+// It checks every variant against an fp64 host reference on sampled rows and times the weight gradient next to the library's
+// in-kernel-split kernel (dlopen of partdistillation_amd/libpd_hip.so when present; the library has no three-plane tn product).
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 #include <math.h>
@@ -31,7 +31,7 @@ struct Dev {
     for (auto &v : h) v = frand(s) * scale;
     CK(hipMalloc(&f, h.size() * 4)); CK(hipMemcpy(f, h.data(), h.size() * 4, hipMemcpyHostToDevice));
     CK(hipMalloc(&p, h.size() * 6));
-    hipLaunchKernelGGL(split3_panels, dim3((unsigned)((h.size() / 4 + 255) / 256)), dim3(256), 0, 0, f, C, p, R, C);
+    hipLaunchKernelGGL(split_planes_panels, dim3((unsigned)((h.size() / 4 + 255) / 256)), dim3(256), 0, 0, f, C, p, R, C);
     CK(hipDeviceSynchronize());
   }
 };
@@ -47,7 +47,6 @@ template <typename F> static float time_us(F &&f, int iters = 20)
   return ms * 1000.f / iters;
 }
 
-typedef int (*tn_fn)(const float *, const float *, const float *, float *, int, int, int, int, int, int, int, void *);
 typedef int (*wg_fn)(const float *, const float *, float *, float *, float *, int64_t, int, int, int, int, int, int, void *);
 typedef int64_t (*wsz_fn)(int, int);
 
@@ -72,7 +71,6 @@ int main(int argc, char **argv)
 {
   const int M = argc > 1 ? atoi(argv[1]) : 43008;
   void *lib = dlopen("partdistillation_amd/libpd_hip.so", RTLD_NOW);
-  tn_fn lib_tn = lib ? (tn_fn)dlsym(lib, "pd_gemm_tn_f32x3") : nullptr;
   wg_fn lib_wg = lib ? (wg_fn)dlsym(lib, "pd_gemm_wgrad_acc_f32x3_ws") : nullptr;
   wsz_fn lib_wsz = lib ? (wsz_fn)dlsym(lib, "pd_gemm_wgrad_f32x3_ws_floats") : nullptr;
   printf("M = %d, library %s\n", M, lib ? "loaded" : "absent");
@@ -85,10 +83,6 @@ int main(int argc, char **argv)
     CK(hipMalloc(&dC, (size_t)M * N * 4));
     const double gf = 2.0 * M * N * K * 1e-9;
     printf("---- tn  C[%d,%d] = A[%d,%d] B[%d,%d]^T  (%.1f GFLOP fp32, x6 bf16 products) relu=%d\n", M, N, M, K, N, K, gf, (int)sh.relu);
-    if (lib_tn) {
-      float us = time_us([&] { lib_tn(A.f, B.f, dbias, dC, M, N, K, K, K, N, sh.relu, nullptr); });
-      printf("  library in-kernel split          : %8.1f us  %6.1f TF fp32-eq  err %.2e\n", us, gf / us * 1e3, check_tn(A, B, bias, dC, M, N, K, sh.relu));
-    }
     struct V { const char *name; int wvm, ns, orient, abl, sched, delay; } vars[] = {
         {"planes 256x256 NS3 dma-spread", 4, 3, 0, 0, 1, 0}, {"planes 128x256 NS2 dma-spread", 2, 2, 0, 0, 1, 0}};
     for (auto v : vars) {
@@ -115,7 +109,6 @@ int main(int argc, char **argv)
       CK(hipMemset(A.p, 0, (size_t)M * K * 6)); CK(hipMemset(B.p, 0, (size_t)N * K * 6)); CK(hipMemset(A.f, 0, (size_t)M * K * 4)); CK(hipMemset(B.f, 0, (size_t)N * K * 4));
       float us = time_us([&] { launch_tn_planes(4, 3, 0, sh.relu ? 1 : 0, 1, A.p, (int64_t)M * K, B.p, (int64_t)N * K, dbias, dC, N, M, N, K, nullptr); });
       printf("  planes 256x256 NS3 dma-spread on ZEROS : %8.1f us\n", us);
-      if (lib_tn) { us = time_us([&] { lib_tn(A.f, B.f, dbias, dC, M, N, K, K, K, N, sh.relu, nullptr); }); printf("  library on ZEROS                       : %8.1f us\n", us); }
     }
     CK(hipFree(A.f)); CK(hipFree(A.p)); CK(hipFree(B.f)); CK(hipFree(B.p)); CK(hipFree(dC)); CK(hipFree(dbias));
   }
