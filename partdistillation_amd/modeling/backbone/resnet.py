@@ -22,6 +22,15 @@ from ...functions.fused import affine_act, max_pool3x3s2, max_pool3x3s2_supporte
 OWN_MAXPOOL = bool(int(__import__("os").environ.get("PD_OWN_MAXPOOL", "1")))    # the stem's max pooling on pd_maxpool3s2_{fwd,bwd}_bf16 (0: ATen)
 OWN_STEM = bool(int(__import__("os").environ.get("PD_OWN_STEM", "1")))          # the 7 x 7 stem on pd_stem7x7_{fwd,wgrad} (0: MIOpen + pd_affine_act)
 OWN_WGRAD = bool(int(__import__("os").environ.get("PD_CONV_OWN_WGRAD", "1")))   # 0: MIOpen's filter gradients (tools/ comparisons)
+OWN_FP32 = bool(int(__import__("os").environ.get("PD_R50_FP32_OWN", "0")))      # 1: fp32 runs (autocast off) on pd_conv_f32_* / pd_stem7x7_f32_* (0: MIOpen)
+
+
+def _own_fp32(x):
+    """functions/conv_f32 when an fp32 run (no autocast) is switched to the own kernels, else None; imported only then"""
+    if OWN_FP32 and x.is_cuda and x.dtype == torch.float32 and not torch.is_autocast_enabled():
+        from ...functions import conv_f32
+        return conv_f32
+    return None
 
 
 def _conv_bn_act(conv, x, residual=None, relu=True, fork=False):
@@ -42,6 +51,10 @@ def _conv_bn_act(conv, x, residual=None, relu=True, fork=False):
             y = F.conv2d(x, conv.weight, None, conv.stride, conv.padding, conv.dilation, conv.groups)
         scale, bias = norm.scale_bias()
         return affine_act(y, scale, bias, residual, relu, fork=fork)
+    conv_f32 = _own_fp32(x) if frozen else None
+    if conv_f32 is not None and conv_f32.supported(x, conv):
+        y = conv_f32.conv_module(x, conv, residual, relu)           # convolution + affine + residual + ReLU: one launch (include/pd_conv_f32.h)
+        return (y, y) if fork else y
     if frozen:
         scale, bias = norm.scale_bias()
         w = conv.weight * scale.view(-1, 1, 1, 1).to(conv.weight.dtype)
@@ -66,6 +79,8 @@ class BasicStem(nn.Module):
     def forward(self, x):
         if OWN_STEM and _stem.supported(x, self.conv1):
             x = _stem.stem_conv(x, self.conv1)                      # convolution + frozen-BN affine + ReLU: one launch (include/pd_stem.h)
+        elif _own_fp32(x) is not None and _own_fp32(x).stem_supported(x, self.conv1):
+            x = _own_fp32(x).stem_conv(x, self.conv1)               # the same in fp32 (include/pd_conv_f32.h)
         else:
             x = _conv_bn_act(self.conv1, x)
         if OWN_MAXPOOL and max_pool3x3s2_supported(x):
