@@ -41,7 +41,7 @@ typedef struct PdIgemm {
   const float *scale, *bias;          /* fp32 [n], nullable: acc * scale + bias */
   const void *res;                    /* bf16, nullable: + res (before act / gate), indexed per res_mode */
   const void *res2;                   /* bf16 [m][n], nullable: a second, dense addend (a gradient arriving from outside the backbone) */
-  const void *gate;                   /* bf16 [m][n], nullable: see gate_mode (applied last) */
+  const void *gate;                   /* bf16 [m][n], nullable: see gate_mode (applied last); ignored (never read) when gate_mode == PD_IG_GATE_NONE */
   void *out;                          /* bf16 [m][n] */
   void *out_pre;                      /* bf16 [m][n], nullable: the value BEFORE act (fc1's pre-activation for GELU') */
   int32_t batch, hs, ws, cs;          /* source grid and channels */
@@ -63,11 +63,12 @@ int pd_igemm_bf16(const PdIgemm *p, void *workspace, int64_t workspace_bytes, vo
 int pd_igemm_bf16_supported(int cs, int n, int k, int stride, int pad);
 
 /* `count` problems enqueued back to back on `stream` by ONE call (they run in order and share the workspace, which must hold the
- * largest need: pd_igemm_bf16_seq_workspace_bytes).  The list is host memory and is read before the call returns. */
+ * largest need: pd_igemm_bf16_seq_workspace_bytes).  The list is host memory and is read before the call returns.  A problem that is refused
+ * ends the call with its error: the problems in front of it have been enqueued, it and the ones behind it have not. */
 int64_t pd_igemm_bf16_seq_workspace_bytes(const PdIgemm *list, int count);
 int pd_igemm_bf16_seq(const PdIgemm *list, int count, void *workspace, int64_t workspace_bytes, void *stream);
 
-/* dst[ci][tap][co] = src[co][tap][ci] (* scale[co]) for `count` filters in ONE launch: the [ci][taps][co] operands of the input gradients, rebuilt
+/* dst[ci][tap][co] = src[co][tap][ci] (* scale[co]) for `count` >= 1 filters (count <= 0: PD_ERR_INVALID_ARG) in ONE launch: the [ci][taps][co] operands of the input gradients, rebuilt
  * from the updated weights once per step.  co % 64 == ci % 64 == 0.  table_host_pinned / table_device: caller-provided staging of
  * pd_filter_transpose_table_bytes(count) bytes each; the pinned one must stay untouched until the asynchronous copy has executed. */
 typedef struct PdFilterTranspose {
@@ -83,7 +84,8 @@ int pd_filter_transpose_grouped(const PdFilterTranspose *descs, int count, void 
  *   dw[n][k] = row_scale[n] * sum_m dy[m][n] * x[m][k]   (bf16 operands, fp32 accumulation; result bf16, or fp32 with dw_f32; row stride ldw elements)
  *   db[n]   += sum_m dy[m][n]                            (fp32, nullable; the caller zero-fills or accumulates)
  * What autograd's MmBackward / ConvolutionBackward(weight) computes for nn.Linear (swin.py:34-36, 127-129, 312) under bf16 autocast.
- * n, k, ldy, ldx multiples of 8; operands 16-byte aligned.  Two launches when the rows are cut into slices (fp32 partial tiles, then their sum in
+ * n, k, ldy, ldx multiples of 8, ldy >= n, ldx >= k; dy and x 16-byte aligned.  dw is written one element per store: any ldw >= k (no multiple
+ * required), dw aligned to its element (2 bytes, 4 with dw_f32).  PD_ERR_INVALID_ARG otherwise.  Two launches when the rows are cut into slices (fp32 partial tiles, then their sum in
  * slice order: deterministic).  workspace: pd_wgrad_bf16_workspace_bytes(p) bytes, no initial state; its first 16 KB are never touched, so the
  * buffer that holds pd_igemm_bf16's tickets can be passed. */
 typedef struct PdWgrad {

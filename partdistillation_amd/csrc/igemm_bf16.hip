@@ -490,7 +490,8 @@ int make_plan(const PdIgemm *p, Plan &pl)
     return pd_set_error(PD_ERR_INVALID_ARG, "pd_igemm_bf16: PD_IG_RES_UP2 needs an even result grid");
   IgArgs &a = pl.a;
   a.S = (const bf16_t *)p->src; a.Wf = (const bf16_t *)p->w; a.scale = p->scale; a.bias = p->bias;
-  a.res = (const bf16_t *)p->res; a.res2 = (const bf16_t *)p->res2; a.gate = (const bf16_t *)p->gate; a.Y = (bf16_t *)p->out; a.Ypre = (bf16_t *)p->out_pre;
+  a.res = (const bf16_t *)p->res; a.res2 = (const bf16_t *)p->res2; a.Y = (bf16_t *)p->out; a.Ypre = (bf16_t *)p->out_pre;
+  a.gate = p->gate_mode == PD_IG_GATE_NONE ? nullptr : (const bf16_t *)p->gate;   // (the epilogue keys on the pointer: NONE means no gate, whatever it holds)
   a.slabs = nullptr; a.tickets = nullptr;
   const int64_t M = (int64_t)p->batch * p->ho * p->wo;
   if (M > 0x7fffffff / 2 || (int64_t)p->batch * p->hs * p->ws > 0x7fffffff / 2) return pd_set_error(PD_ERR_INVALID_ARG, "pd_igemm_bf16: grid too large");
@@ -689,7 +690,7 @@ extern "C" int64_t pd_filter_transpose_table_bytes(int count) { return (int64_t)
 
 extern "C" int pd_filter_transpose_grouped(const PdFilterTranspose *descs, int count, void *table_host_pinned, void *table_device, void *stream)
 {
-  if (count <= 0) return PD_OK;
+  if (count <= 0) return pd_set_error(PD_ERR_INVALID_ARG, "pd_filter_transpose_grouped: count=%d (at least one filter)", count);
   if (!descs || !table_host_pinned || !table_device) return pd_set_error(PD_ERR_INVALID_ARG, "pd_filter_transpose_grouped: null pointer");
   TrProblem *h = reinterpret_cast<TrProblem *>(table_host_pinned);
   int blocks = 0;

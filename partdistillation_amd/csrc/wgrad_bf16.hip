@@ -347,9 +347,11 @@ int wg_plan(const PdWgrad *p, WgPlan &pl)
   if (!p || !p->dy || !p->x || !p->dw) return pd_set_error(PD_ERR_INVALID_ARG, "pd_wgrad_bf16: null pointer");
   if (p->m <= 0 || p->n <= 0 || p->k <= 0) return pd_set_error(PD_ERR_INVALID_ARG, "pd_wgrad_bf16: empty problem");
   if ((p->n & 7) || (p->k & 7) || (p->ldy & 7) || (p->ldx & 7) || p->ldy < p->n || p->ldx < p->k || p->ldw < p->k)
-    return pd_set_error(PD_ERR_INVALID_ARG, "pd_wgrad_bf16: n, k and the operands' row strides must be multiples of 8 (n=%d k=%d ldy=%d ldx=%d ldw=%d)", p->n,
-                        p->k, p->ldy, p->ldx, p->ldw);
+    return pd_set_error(PD_ERR_INVALID_ARG, "pd_wgrad_bf16: n, k, ldy and ldx must be multiples of 8, ldy >= n, ldx >= k, ldw >= k (n=%d k=%d ldy=%d ldx=%d ldw=%d)",
+                        p->n, p->k, p->ldy, p->ldx, p->ldw);
   if (((uintptr_t)p->dy | (uintptr_t)p->x) & 15) return pd_set_error(PD_ERR_INVALID_ARG, "pd_wgrad_bf16: operands must be 16-byte aligned");
+  // dW is written one element per store: any ldw >= k, and only the element's own alignment
+  if ((uintptr_t)p->dw & (p->dw_f32 ? 3 : 1)) return pd_set_error(PD_ERR_INVALID_ARG, "pd_wgrad_bf16: dw must be aligned to its element size");
   WgArgs &a = pl.a;
   a.dY = (const bf16_t *)p->dy; a.X = (const bf16_t *)p->x; a.dW = (bf16_t *)p->dw; a.dB = p->db; a.rscale = p->row_scale;
   a.slabs = nullptr; a.mode = g_wg_mode;
