@@ -2,7 +2,6 @@
 frozen-BN affine + residual add + ReLU; the input gradient = transposed convolution + the gradient arriving over the
 shortcut.  GPU only; no fallback."""
 import contextlib
-import ctypes
 import weakref
 
 import os
@@ -11,6 +10,7 @@ import torch
 from torch.autograd import Function
 
 from .. import lib as _lib
+from . import grouped_launch as _grouped
 
 
 def _stream():
@@ -59,7 +59,9 @@ def transposed_filter(w):
     return w.permute(1, 2, 3, 0).contiguous()
 
 
-_WS = {}
+def wgrad_workspace(device, need):
+    """the fp32 scratch every bf16 filter-gradient launch on a stream shares (grouped_launch.workspace)"""
+    return _grouped.workspace("conv wgrad", device, need, 1 << 24)
 
 
 def conv_wgrad(dz, x, k, stride=1, pad=0, like=None):
@@ -68,9 +70,7 @@ def conv_wgrad(dz, x, k, stride=1, pad=0, like=None):
     co, Ho, Wo = dz.shape[1], dz.shape[2], dz.shape[3]
     L = _lib.load()
     need = int(L.pd_conv_bf16_wgrad_workspace_floats(B, Ho, Wo, ci, co, k))
-    ws = _WS.get(str(x.device))
-    if ws is None or ws.numel() < need:
-        ws = _WS[str(x.device)] = torch.empty(max(need, 1 << 24), dtype=torch.float32, device=x.device)
+    ws = wgrad_workspace(x.device, need)
     dwk = torch.empty((co, k, k, ci), dtype=torch.bfloat16, device=x.device)
     with torch.cuda.device(x.device):
         rc = L.pd_conv_bf16_wgrad(dz.data_ptr(), x.data_ptr(), dwk.data_ptr(), ws.data_ptr(), ws.numel(), B, H, W, ci, Ho, Wo, co, k, stride, pad,
@@ -91,8 +91,6 @@ class _Deferred:
     queue = []
     adopt = []                                               # (weakref(filter), address handed to autograd): verify_adopted()
     queued = set()                                           # id(filter) of every filter with a gradient in the queue: a second use computes now
-    ring = None
-    table_dev = None
     MAXP = 256
 
 
@@ -170,7 +168,6 @@ def _run(q):
     if not q:
         return
     dev = q[0][0][0].device
-    L = _lib.load()
     for lo in range(0, len(q), _Deferred.MAXP):
         part = q[lo:lo + _Deferred.MAXP]
         descs = (_Desc * len(part))()
@@ -180,33 +177,16 @@ def _run(q):
             d.db = entry[5] if len(entry) > 5 else None
             d.scale = entry[6] if len(entry) > 6 else None
             d.batch, d.hi, d.wi, d.ci, d.ho, d.wo, d.co, d.k, d.stride, d.pad = geom
-        from .. import cmdbuf
-        need = int(L.pd_conv_bf16_wgrad_grouped_workspace_floats(ctypes.byref(descs), len(part)))
-        tbytes = int(L.pd_conv_bf16_wgrad_grouped_table_bytes(_Deferred.MAXP))
-        if _Deferred.ring is None:
-            from .fused import PinnedRing
-            with cmdbuf.host_ops():
-                _Deferred.ring = PinnedRing(tbytes, torch.uint8, pin=True)
-        if cmdbuf.active() is not None:                          # recorded region: scratch + table in its arena, operands must be stable
-            for entry in part:
-                for ptr, nm in ((entry[1], "dz"), (entry[2], "x"), (entry[3], "dw"), (entry[5] if len(entry) > 5 else None, "db")):
-                    if ptr:
-                        cmdbuf.require_stable(ptr, "grouped filter gradient operand " + nm)
-            ws = torch.empty(max(need, 1), dtype=torch.float32, device=dev)
-            table_dev = torch.empty(tbytes, dtype=torch.uint8, device=dev)
-        else:
-            ws = _WS.get(str(dev))
-            if ws is None or ws.numel() < need:
-                ws = _WS[str(dev)] = torch.empty(max(need, 1 << 24), dtype=torch.float32, device=dev)
-            if _Deferred.table_dev is None or _Deferred.table_dev.device != dev:
-                _Deferred.table_dev = torch.empty(tbytes, dtype=torch.uint8, device=dev)
-            table_dev = _Deferred.table_dev
-        host = _Deferred.ring.acquire()
-        with torch.cuda.device(dev):
-            rc = L.pd_conv_bf16_wgrad_grouped(ctypes.byref(descs), len(part), host.data_ptr(), table_dev.data_ptr(), ws.data_ptr(),
-                                              ws.numel(), _stream())
-        _Deferred.ring.release()
-        _lib.check(rc)
+            _grouped.require_stable(((dzp, "dz"), (xp, "x"), (dwp, "dw"), (d.db, "db")), "grouped filter gradient operand")
+        launch_grouped(descs, len(part), dev)
+
+
+def launch_grouped(descs, count, dev):
+    """pd_conv_bf16_wgrad_grouped over the first `count` descriptors of a ctypes array of _Desc (count <= _Deferred.MAXP)"""
+    need = int(_lib.load().pd_conv_bf16_wgrad_grouped_workspace_floats(descs, count))
+    ws = wgrad_workspace(dev, need)
+    _grouped.launch("pd_conv_bf16_wgrad_grouped", descs, count, table_bytes="pd_conv_bf16_wgrad_grouped_table_bytes",
+                    post=(ws.data_ptr(), ws.numel()), device=dev)
 
 
 GEMM_1X1_FWD = os.environ.get("PD_GEMM_1X1_FWD", "0") != "0"

@@ -6,6 +6,7 @@ Reference: transformer_decoder/mask2former_transformer_decoder.py:395-439 (the l
 import torch
 
 from .. import lib as _lib
+from . import grouped_launch as _grouped
 
 C, FF = 256, 2048
 bf16 = torch.bfloat16
@@ -26,45 +27,25 @@ def supported(C_, ff, cdt):
 _PackDesc = _lib.struct("PdDecPack")
 
 
-_PK = {}
-
-
 def pack(weights, transpose=False):
     """[N_i, K_i] bf16 row-major weights -> their packed copies (pd_dec_pack_grouped: block order of the fused kernels' weight stream), of
     the weights themselves (forward kernels) or of their transposes (backward kernels), all in ONE launch into one fresh buffer.
-    -> list of flat bf16 tensors.  The descriptor table is cached per list of (address, shape)."""
-    from .fused import PinnedRing
-    key = (tuple((w.data_ptr(), tuple(w.shape)) for w in weights), bool(transpose))
-    L = _lib.load()
+    -> list of flat bf16 tensors"""
+    offs, total = [], 0
+    for w in weights:
+        assert w.dtype == bf16 and w.is_contiguous() and w.dim() == 2
+        n, k = (w.shape[1], w.shape[0]) if transpose else w.shape
+        assert n % 32 == 0 and k % 256 == 0, (n, k)
+        offs.append(total)
+        total += w.numel()
     dev = weights[0].device
-    hit = _PK.get(key)
-    if hit is None:
-        offs, total = [], 0
-        for w in weights:
-            assert w.dtype == bf16 and w.is_contiguous() and w.dim() == 2
-            n, k = (w.shape[1], w.shape[0]) if transpose else w.shape
-            assert n % 32 == 0 and k % 256 == 0, (n, k)
-            offs.append(total)
-            total += w.numel()
-        tb = int(L.pd_dec_pack_table_bytes(len(weights)))
-        hit = _PK[key] = ((_PackDesc * len(weights))(), offs, total, PinnedRing(tb, torch.uint8, pin=True), torch.empty(tb, dtype=torch.uint8, device=dev))
-        if len(_PK) > 16:
-            _PK.pop(next(iter(_PK)))
-    descs, offs, total, ring, tdev = hit
-    from .. import cmdbuf
-    if cmdbuf.active() is not None:                          # recorded region: its own descriptor array + device table (arena)
-        descs = (_PackDesc * len(weights))()
-        tdev = torch.empty(tdev.numel(), dtype=torch.uint8, device=dev)
-        for w in weights:
-            cmdbuf.require_stable(w.data_ptr(), "weight to pack")
     buf = torch.empty(total, dtype=bf16, device=dev)
     base = buf.data_ptr()
+    descs = (_PackDesc * len(weights))()
     for d, w, o in zip(descs, weights, offs):
         d.src, d.dst, d.rows, d.cols, d.transpose = w.data_ptr(), base + 2 * o, w.shape[0], w.shape[1], int(bool(transpose))
-    host = ring.acquire()
-    rc = L.pd_dec_pack_grouped(descs, len(weights), host.data_ptr(), tdev.data_ptr(), _stream())
-    ring.release()
-    _lib.check(rc)
+    _grouped.require_stable(((w, str(i)) for i, w in enumerate(weights)), "weight to pack")
+    _grouped.launch("pd_dec_pack_grouped", descs, len(weights), table_bytes="pd_dec_pack_table_bytes", device=dev)
     return [buf[o:o + w.numel()] for w, o in zip(weights, offs)]
 
 

@@ -8,12 +8,12 @@ from functools import partial
 import torch
 
 from .. import lib as _lib
-from .grouped_launch import as_u8, launch, ptr, require_cuda
+from .grouped_launch import as_u8, launch_fields, ptr, require_cuda
 
 LIMITS = (1, 10, 50, 100, 200)            # AR@k of the proposal evaluator
 MAX_ROWS, MAX_GT = _lib.const("PD_EVAL_MAX_ROWS"), _lib.const("PD_EVAL_MAX_GT")
 _cuda = partial(require_cuda, "pd_eval")
-_launch = partial(launch, table_bytes="pd_eval_table_bytes")
+_launch = partial(launch_fields, table_bytes="pd_eval_table_bytes")
 
 
 PdEvalMaskSet = _lib.struct("PdEvalMaskSet")

@@ -1,11 +1,10 @@
 """fp32 nn.Linear on the matrix cores (pd_gemm_tn_f32 / pd_gemm_wgrad_f32, include/pd_gemm.h): forward, input
 gradient and weight gradient as hand-written MFMA GEMMs; exact fp32 arithmetic (no TF32 / bf16 rounding)."""
-import ctypes
-
 import torch
 from torch.autograd import Function
 
 from .. import lib as _lib
+from . import grouped_launch as _grouped
 
 
 def _stream():
@@ -138,19 +137,9 @@ WGRAD_X3 = True      # weight gradients through the 3-way bf16 split kernel (pd_
                      # False: the exact-fp32 MFMA kernel (pd_gemm_wgrad_acc_f32).
 
 
-_WGRAD_WS = {}
-
-
 def _wgrad_workspace(device, need):
-    """one persistent fp32 scratch per device AND stream for the partial tiles of pd_gemm_wgrad_acc_f32x3_ws (<= 34 MB;
-    consecutive launches on a stream reuse it in order)"""
-    if need <= 0:
-        return None
-    key = (str(device), torch.cuda.current_stream(device).cuda_stream)
-    ws = _WGRAD_WS.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _WGRAD_WS[key] = torch.empty(max(need, 8912896), dtype=torch.float32, device=device)
-    return ws
+    """fp32 scratch for the partial tiles of pd_gemm_wgrad_acc_f32x3_ws (<= 34 MB; grouped_launch.workspace: one per device and stream)"""
+    return _grouped.workspace("gemm wgrad", device, need, 8912896) if need > 0 else None
 
 
 def gemm_wgrad_acc(dy, x, dw, db=None, x3=None, h2=False, y_amax=None, x_amax=None):
@@ -192,9 +181,6 @@ class WgradQueue:
     consumes a weight gradient before the optimizer, so the encoder queues its 30 per step (5 per layer) instead of launching each
     when its operands appear.  The queue keeps the operands alive until flush()."""
     MAXP = 256
-    _ring = None
-    _table_dev = {}
-    _ws = {}
 
     def __init__(self, h2=False):
         """h2: the fp16 two-plane form (pd_gemm_wgrad_f16x2_grouped); add() then takes the operands' absolute row maxima"""
@@ -224,48 +210,25 @@ class WgradQueue:
             parts = [g[lo:lo + self.MAXP] for g in (wide, rest) for lo in range(0, len(g), self.MAXP)]
         else:
             parts = [items[lo:lo + self.MAXP] for lo in range(0, len(items), self.MAXP)]
-        from .. import cmdbuf
+        fn = "pd_gemm_wgrad_f16x2_grouped" if self.h2 else "pd_gemm_wgrad_f32x3_grouped"
         for part in parts:
             descs = (_WgradDesc * len(part))()
             flops = nbytes = 0.0
             for d, (dy, x, dw, db, ya, xa) in zip(descs, part):
-                if cmdbuf.active() is not None:
-                    for t_, nm in ((dy, "dY"), (x, "X"), (dw, "dW"), (db, "dB"), (ya, "y_amax"), (xa, "x_amax")):
-                        if t_ is not None:
-                            cmdbuf.require_stable(t_.data_ptr(), "grouped weight gradient operand " + nm)
+                _grouped.require_stable(((dy, "dY"), (x, "X"), (dw, "dW"), (db, "dB"), (ya, "y_amax"), (xa, "x_amax")), "grouped weight gradient operand")
                 d.dY, d.X, d.dW, d.dB = dy.data_ptr(), x.data_ptr(), dw.data_ptr(), (db.data_ptr() if db is not None else None)
                 d.y_amax, d.x_amax = (ya.data_ptr() if ya is not None else None), (xa.data_ptr() if xa is not None else None)
                 d.M, d.N, d.K, d.ldy, d.ldx, d.ldw = dy.shape[0], dy.shape[1], x.shape[1], dy.stride(0), x.stride(0), dw.shape[1]
                 flops += 2.0 * dy.shape[0] * dy.shape[1] * x.shape[1]
                 nbytes += 4.0 * (dy.shape[0] * (dy.shape[1] + x.shape[1]) + dy.shape[1] * x.shape[1])
-            need = int((L.pd_gemm_wgrad_f16x2_grouped_ws_floats if self.h2 else L.pd_gemm_wgrad_f32x3_grouped_ws_floats)(ctypes.byref(descs), len(part)))
+            need = int(getattr(L, fn + "_ws_floats")(descs, len(part)))
             if need < 0:
                 raise RuntimeError("pd_gemm_wgrad_f32x3_grouped: a queued problem violates the alignment rules (N, K, strides % 4, 16-byte bases)")
-            tbytes = int(L.pd_gemm_wgrad_f32x3_grouped_table_bytes(self.MAXP))
-            if WgradQueue._ring is None:
-                from .fused import PinnedRing
-                with cmdbuf.host_ops():
-                    WgradQueue._ring = PinnedRing(tbytes, torch.uint8, pin=True)
-            if cmdbuf.active() is not None:                       # recorded region: scratch + table owned by the recording (its arena)
-                ws = torch.empty(max(need, 1), dtype=torch.float32, device=dev)
-                tdev = torch.empty(tbytes, dtype=torch.uint8, device=dev)
-            else:
-                key = (str(dev), torch.cuda.current_stream(dev).cuda_stream)
-                ws = WgradQueue._ws.get(key)
-                if ws is None or ws.numel() < need:
-                    ws = WgradQueue._ws[key] = torch.empty(max(need, 1 << 24), dtype=torch.float32, device=dev)
-                tdev = WgradQueue._table_dev.get(str(dev))
-                if tdev is None:
-                    tdev = WgradQueue._table_dev[str(dev)] = torch.empty(tbytes, dtype=torch.uint8, device=dev)
-            host = WgradQueue._ring.acquire()
+            ws = _grouped.workspace("gemm wgrad grouped", dev, need, 1 << 24)
             if _TIMING["on"]:
                 a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 a.record()
-            with torch.cuda.device(dev):
-                fn = L.pd_gemm_wgrad_f16x2_grouped if self.h2 else L.pd_gemm_wgrad_f32x3_grouped
-                rc = fn(ctypes.byref(descs), len(part), host.data_ptr(), tdev.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
-            WgradQueue._ring.release()
-            _lib.check(rc)
+            _grouped.launch(fn, descs, len(part), table_bytes="pd_gemm_wgrad_f32x3_grouped_table_bytes", post=(ws.data_ptr(), ws.numel()), device=dev)
             if _TIMING["on"]:
                 b.record()
                 _TIMING["wgrad"].append((a, b, (flops, nbytes, "h2 grouped" if self.h2 else "x3 grouped")))

@@ -5,6 +5,7 @@ import ctypes
 import torch
 
 from .. import lib as _lib
+from . import grouped_launch as _grouped
 
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
 GATE_NONE, GATE_RELU, GATE_GELU = 0, 1, 2
@@ -106,45 +107,22 @@ def conv_dgrad_nhwc(dz, wt, in_hw, *, k, stride=1, pad=0, res=None, gate=None, g
                gate_mode=gate_mode, res_mode=res_mode)
 
 
-_TR = {}
-
-
 def transposed(weights):
     """[N_i, K_i] bf16 row-major weights -> their [K_i, N_i] transposes (the "weight" operand of the input-gradient GEMMs), all in ONE
-    grouped launch into one fresh buffer; the descriptor table is cached per list of weight addresses"""
-    from .fused import PinnedRing
-    # (address AND shape: the allocator hands a freed model's addresses to the next one, whose layers may be shaped differently — offsets and
-    #  buffer size cached under the bare addresses would then be another model's: out-of-bounds transposes)
-    key = tuple((w.data_ptr(), tuple(w.shape)) for w in weights)
-    L = _lib.load()
+    grouped launch into one fresh buffer"""
+    offs, total = [], 0
+    for w in weights:
+        assert w.dtype == torch.bfloat16 and w.is_contiguous() and w.dim() == 2
+        offs.append(total)
+        total += (w.numel() + 127) // 128 * 128
     dev = weights[0].device
-    hit = _TR.get(key)
-    if hit is None:
-        descs = (PdFilterTranspose * len(weights))()
-        offs, total = [], 0
-        for w in weights:
-            assert w.dtype == torch.bfloat16 and w.is_contiguous() and w.dim() == 2
-            offs.append(total)
-            total += (w.numel() + 127) // 128 * 128
-        tb = int(L.pd_filter_transpose_table_bytes(len(weights)))
-        hit = _TR[key] = (descs, offs, total, PinnedRing(tb, torch.uint8, pin=True), torch.empty(tb, dtype=torch.uint8, device=dev))
-        if len(_TR) > 64:
-            _TR.pop(next(iter(_TR)))
-    descs, offs, total, ring, tdev = hit
-    from .. import cmdbuf
-    if cmdbuf.active() is not None:                          # recorded region: its own descriptor array + device table (arena)
-        descs = (PdFilterTranspose * len(weights))()
-        tdev = torch.empty(tdev.numel(), dtype=torch.uint8, device=dev)
-        for w in weights:
-            cmdbuf.require_stable(w.data_ptr(), "weight to transpose")
     buf = torch.empty(total, dtype=torch.bfloat16, device=dev)
     base = buf.data_ptr()
+    descs = (PdFilterTranspose * len(weights))()
     for d, w, o in zip(descs, weights, offs):
         d.src, d.dst, d.scale, d.co, d.taps, d.ci = w.data_ptr(), base + 2 * o, None, w.shape[0], 1, w.shape[1]
-    host = ring.acquire()
-    rc = L.pd_filter_transpose_grouped(descs, len(weights), host.data_ptr(), tdev.data_ptr(), _lib.current_stream())
-    ring.release()
-    _lib.check(rc)
+    _grouped.require_stable(((w, str(i)) for i, w in enumerate(weights)), "weight to transpose")
+    _grouped.launch("pd_filter_transpose_grouped", descs, len(weights), table_bytes="pd_filter_transpose_table_bytes", device=dev)
     return [buf[o:o + w.numel()].view(w.shape[1], w.shape[0]) for w, o in zip(weights, offs)]
 
 

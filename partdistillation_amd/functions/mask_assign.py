@@ -6,12 +6,12 @@ from functools import partial
 import torch
 
 from .. import lib as _lib
-from .grouped_launch import as_u8, launch, require_cuda
+from .grouped_launch import as_u8, launch_fields, require_cuda
 
 MAX_K, MAX_KEYS, MAX_GT = (_lib.const(n) for n in ("PD_ASSIGN_MAX_K", "PD_ASSIGN_MAX_KEYS", "PD_ASSIGN_MAX_GT"))
 MAX_Q = _lib.const("PD_ASSIGN_MAX_Q")
 _cuda = partial(require_cuda, "pd_assign")
-_launch = partial(launch, table_bytes="pd_assign_table_bytes")
+_launch = partial(launch_fields, table_bytes="pd_assign_table_bytes")
 
 
 PdAssignResized = _lib.struct("PdAssignResized")

@@ -6,6 +6,7 @@ import ctypes
 import torch
 
 from .. import lib as _lib
+from . import grouped_launch as _grouped
 from .igemm import ACT_GELU, ACT_NONE, GATE_GELU, GATE_NONE   # noqa: F401  (same epilogue vocabulary as pd_igemm_bf16)
 
 E4M3, E5M2 = 0, 1
@@ -39,42 +40,22 @@ def quantize(x, fmt=E4M3):
     return q, s
 
 
-_QT = {}
-
-
 def quantize_grouped(tensors, fmt=E4M3):
     """contiguous bf16 [n_i, k_i] tensors (k_i % 32 == 0: the weights of a stage) -> [(q_i [n_i, k_i], s_i [n_i, k_i / 32])], ONE launch into
-    two fresh flat buffers; the staging of the descriptor table is cached per list of addresses"""
-    from .fused import PinnedRing
-    from .. import cmdbuf
-    L = _lib.load()
+    two fresh flat buffers"""
+    offs, total = [], 0
+    for t in tensors:
+        assert t.dtype == torch.bfloat16 and t.is_contiguous() and t.dim() == 2 and t.shape[1] % BLOCK == 0, (t.dtype, t.shape)
+        offs.append(total)
+        total += (t.numel() + 127) // 128 * 128
     dev = tensors[0].device
-    key = tuple((t.data_ptr(), tuple(t.shape)) for t in tensors)       # (address and shape: a re-used address may hold another model's layer)
-    hit = _QT.get(key)
-    if hit is None:
-        offs, total = [], 0
-        for t in tensors:
-            assert t.dtype == torch.bfloat16 and t.is_contiguous() and t.dim() == 2 and t.shape[1] % BLOCK == 0, (t.dtype, t.shape)
-            offs.append(total)
-            total += (t.numel() + 127) // 128 * 128
-        tb = int(L.pd_mx8_quantize_table_bytes(len(tensors)))
-        hit = _QT[key] = (offs, total, PinnedRing(tb, torch.uint8, pin=True), torch.empty(tb, dtype=torch.uint8, device=dev))
-        if len(_QT) > 64:
-            _QT.pop(next(iter(_QT)))
-    offs, total, ring, tdev = hit
-    if cmdbuf.active() is not None:                          # recorded region: its own device table (arena); the sources must not move
-        tdev = torch.empty(tdev.numel(), dtype=torch.uint8, device=dev)
-        for t in tensors:
-            cmdbuf.require_stable(t.data_ptr(), "weight to quantise")
     qbuf = torch.empty(total, dtype=torch.uint8, device=dev)
     sbuf = torch.empty(total // BLOCK, dtype=torch.uint8, device=dev)
     descs = (PdMx8Tensor * len(tensors))()
     for d, t, o in zip(descs, tensors, offs):
         d.x, d.q, d.s, d.numel = t.data_ptr(), qbuf.data_ptr() + o, sbuf.data_ptr() + o // BLOCK, t.numel()
-    host = ring.acquire()
-    rc = L.pd_mx8_quantize_grouped(descs, len(tensors), fmt, host.data_ptr(), tdev.data_ptr(), _lib.current_stream())
-    ring.release()
-    _lib.check(rc)
+    _grouped.require_stable(((t, str(i)) for i, t in enumerate(tensors)), "weight to quantise")
+    _grouped.launch("pd_mx8_quantize_grouped", descs, len(tensors), table_bytes="pd_mx8_quantize_table_bytes", pre=(fmt,), device=dev)
     return [(qbuf[o:o + t.numel()].view(t.shape), sbuf[o // BLOCK:(o + t.numel()) // BLOCK].view(t.shape[0], t.shape[1] // BLOCK))
             for t, o in zip(tensors, offs)]
 

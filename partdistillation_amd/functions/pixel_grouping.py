@@ -6,11 +6,11 @@ from functools import partial
 import torch
 
 from .. import lib as _lib
-from .grouped_launch import as_u8, launch, require_cuda
+from .grouped_launch import as_u8, launch_fields, require_cuda
 
 MAX_K = _lib.const("PD_GROUPING_MAX_K")
 _cuda = partial(require_cuda, "pd_grouping")
-_launch = partial(launch, table_bytes="pd_grouping_table_bytes")
+_launch = partial(launch_fields, table_bytes="pd_grouping_table_bytes")
 
 
 PdGroupLabels = _lib.struct("PdGroupLabels")

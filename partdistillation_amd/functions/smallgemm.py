@@ -5,6 +5,7 @@ import ctypes
 import torch
 
 from .. import lib as _lib
+from . import grouped_launch as _grouped
 
 
 def _stream():
@@ -154,8 +155,6 @@ class WgradQueue:
     """weight gradients of one backward pass collected and run as ONE launch (pd_sgemm_wgrad_grouped_bf16).  add() allocates the
     output and keeps the operands alive; run() launches and forgets them.  Same arithmetic as wgrad()."""
     MAXP = 128
-    _ring = None
-    _table_dev = {}
 
     def __init__(self):
         self.items = []
@@ -173,34 +172,13 @@ class WgradQueue:
         items, self.items = self.items, []
         if not items:
             return
-        L = _lib.load()
         dev = items[0][0].device
-        cls = WgradQueue
-        for lo in range(0, len(items), cls.MAXP):
-            part = items[lo:lo + cls.MAXP]
+        for lo in range(0, len(items), self.MAXP):
+            part = items[lo:lo + self.MAXP]
             descs = (_WgradDesc * len(part))()
             for d, (dy, x, dw, db) in zip(descs, part):
+                _grouped.require_stable(((dy, "dY"), (x, "X"), (dw, "dW"), (db, "dB")), "grouped skinny weight gradient operand")
                 d.dY, d.X, d.dW, d.dB = dy.data_ptr(), x.data_ptr(), dw.data_ptr(), (db.data_ptr() if db is not None else None)
                 d.M, d.N, d.K = dy.shape[0], dy.shape[1], x.shape[1]
                 d.ldy, d.ldx, d.ldw = dy.stride(0), x.stride(0), dw.stride(0)
-            from .. import cmdbuf
-            tbytes = int(L.pd_sgemm_wgrad_grouped_table_bytes(cls.MAXP))
-            if cls._ring is None:
-                from .fused import PinnedRing
-                with cmdbuf.host_ops():
-                    cls._ring = PinnedRing(tbytes, torch.uint8, pin=True)
-            if cmdbuf.active() is not None:
-                for dy, x, dw, db in part:
-                    for t_, nm in ((dy, "dY"), (x, "X"), (dw, "dW"), (db, "dB")):
-                        if t_ is not None:
-                            cmdbuf.require_stable(t_.data_ptr(), "grouped skinny weight gradient operand " + nm)
-                tab = torch.empty(tbytes, dtype=torch.uint8, device=dev)
-            else:
-                tab = cls._table_dev.get(str(dev))
-                if tab is None:
-                    tab = cls._table_dev[str(dev)] = torch.empty(tbytes, dtype=torch.uint8, device=dev)
-            host = cls._ring.acquire()
-            with torch.cuda.device(dev):
-                rc = L.pd_sgemm_wgrad_grouped_bf16(ctypes.byref(descs), len(part), host.data_ptr(), tab.data_ptr(), _stream())
-            cls._ring.release()
-            _lib.check(rc)
+            _grouped.launch("pd_sgemm_wgrad_grouped_bf16", descs, len(part), table_bytes="pd_sgemm_wgrad_grouped_table_bytes", device=dev)

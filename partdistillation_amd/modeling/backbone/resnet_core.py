@@ -23,8 +23,7 @@ from torch.autograd import Function
 
 from ... import lib as _lib
 from ...compat.layers import FrozenBatchNorm2d
-from ...functions import conv_bf16, igemm
-from ...functions.fused import PinnedRing
+from ...functions import conv_bf16, grouped_launch, igemm
 
 # one Plan (= one persistent arena holding every activation, gradient, transposed filter and filter gradient of the body: ~3.5 GB at
 # 2 x 1024^2) per (network, input shape, grad mode) — bounded, least recently used first: the reference's mappers crop / resize to
@@ -252,9 +251,6 @@ class Plan:
         self.tr_descs = (igemm.PdFilterTranspose * len(self.tr))()
         for t, c in zip(self.tr_descs, self.tr):
             t.src, t.dst, t.scale, t.co, t.taps, t.ci = c.mod.weight.data_ptr(), self.ptr(c.wt_off), c.scale.data_ptr(), c.co, c.k * c.k, c.ci
-        tb = int(L.pd_filter_transpose_table_bytes(len(self.tr)))
-        self.tr_ring = PinnedRing(tb, torch.uint8, pin=True)
-        self.tr_dev = torch.empty(tb, dtype=torch.uint8, device=self.dev)
         self.wg_all = wg
         self._wg_cache = {}
 
@@ -299,9 +295,7 @@ class Plan:
         st = _lib.current_stream()
         B = self.shape[0]
         # transposed + scaled filters of this step's weights
-        host = self.tr_ring.acquire()
-        _lib.check(L.pd_filter_transpose_grouped(self.tr_descs, len(self.tr), host.data_ptr(), self.tr_dev.data_ptr(), st))
-        self.tr_ring.release()
+        grouped_launch.launch("pd_filter_transpose_grouped", self.tr_descs, len(self.tr), table_bytes="pd_filter_transpose_table_bytes", device=self.dev)
         keep = []
         gmap = dict(zip(self.out_names, gouts))
 
@@ -348,20 +342,7 @@ class Plan:
             p0 = x0.data_ptr()
             for j in x0_idx:
                 arr[j].x = p0
-            need = int(L.pd_conv_bf16_wgrad_grouped_workspace_floats(arr, n))
-            wsf = conv_bf16._WS.get(str(self.dev))
-            if wsf is None or wsf.numel() < need:
-                wsf = conv_bf16._WS[str(self.dev)] = torch.empty(max(need, 1 << 24), dtype=torch.float32, device=self.dev)
-            D = conv_bf16._Deferred
-            tbytes = int(L.pd_conv_bf16_wgrad_grouped_table_bytes(D.MAXP))
-            if D.ring is None:
-                D.ring = PinnedRing(tbytes, torch.uint8, pin=True)
-            if D.table_dev is None or D.table_dev.device != self.dev:
-                D.table_dev = torch.empty(tbytes, dtype=torch.uint8, device=self.dev)
-            hostt = D.ring.acquire()
-            rc = L.pd_conv_bf16_wgrad_grouped(arr, n, hostt.data_ptr(), D.table_dev.data_ptr(), wsf.data_ptr(), wsf.numel(), st)
-            D.ring.release()
-            _lib.check(rc)
+            conv_bf16.launch_grouped(arr, n, self.dev)
             done = []
             for i in range(lo, hi):
                 c = order[i]

@@ -138,6 +138,23 @@ def test_rows_problems_with_bias_sums_in_the_grouped_launch():
         torch.testing.assert_close(acc - 0.5, dy.float().sum(0), rtol=1e-4, atol=2e-2)
 
 
+def test_rows_problems_in_more_than_one_chunk_of_the_grouped_launch():
+    """260 problems are more than one grouped launch holds (_Deferred.MAXP = 256): the second chunk's table is staged while the first
+    chunk's launch may still be queued.  Distinct operands; every third problem adds its bias gradient into an fp32 accumulator."""
+    from partdistillation_amd.functions import conv_bf16 as C
+    P, M, N, K = 260, 40, 64, 64
+    assert P > C._Deferred.MAXP
+    dy, x = _mk((P, M, N), 500), _mk((P, M, K), 501)
+    dw = torch.empty((P, N, K), dtype=torch.bfloat16, device=DEV)
+    acc = torch.full((P, N), 0.5, device=DEV)
+    C.run_now([C.rows_entry(dy[i], x[i], dw[i], acc[i] if i % 3 == 0 else None) for i in range(P)])
+    ref = dy.float().transpose(1, 2) @ x.float()
+    for i in range(P):
+        assert (dw[i].float() - ref[i]).abs().max().item() <= 2 ** -7 * ref[i].abs().max().item(), i
+    torch.testing.assert_close(acc[::3] - 0.5, dy.float().sum(1)[::3], rtol=1e-4, atol=2e-2)
+    assert torch.equal(acc[1::3], torch.full_like(acc[1::3], 0.5)) and torch.equal(acc[2::3], torch.full_like(acc[2::3], 0.5))
+
+
 def test_conv_rejects_what_it_does_not_cover():
     from partdistillation_amd import lib
     from partdistillation_amd.functions import conv_bf16 as C

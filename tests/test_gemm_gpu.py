@@ -178,6 +178,36 @@ def test_grouped_weight_gradients_match_fp64_and_the_single_launches():
             torch.testing.assert_close(db.double(), db0.double() + dy.double().sum(0), **tol)
 
 
+@pytest.mark.parametrize("h2", [False, True])
+def test_grouped_weight_gradients_in_more_than_one_chunk(h2):
+    """260 queued problems are more than one launch holds (WgradQueue.MAXP = 256): flush() stages the second chunk's table while the
+    first chunk's launch may still be queued.  Distinct operands, each dW (and every fourth problem's dB) accumulated INTO its own
+    pre-filled values, against fp64 with the tolerances of the grouped tests above and below."""
+    from partdistillation_amd.functions import gemm
+    P, M, N, K = 260, 40, 8, 12
+    assert P > gemm.WgradQueue.MAXP
+    g = torch.Generator(device="cuda").manual_seed(260)
+    dy, x = torch.randn(P, M, N, device="cuda", generator=g), torch.randn(P, M, K, device="cuda", generator=g)
+    dw0, db0 = torch.randn(P, N, K, device="cuda", generator=g), torch.randn(P, N, device="cuda", generator=g)
+    dw, db = dw0.clone(), db0.clone()
+    ya, xa = (gemm.row_amax(dy.view(-1, N)).view(P, M), gemm.row_amax(x.view(-1, K)).view(P, M)) if h2 else (None, None)
+    q = gemm.WgradQueue(h2=h2)
+    for i in range(P):
+        q.add(dy[i], x[i], dw[i], db[i] if i % 4 == 0 else None, *((ya[i], xa[i]) if h2 else ()))
+    q.flush()
+    assert q.items == []
+    want_w = dw0.double() + dy.double().transpose(1, 2) @ x.double()
+    want_b = db0.double()
+    want_b[::4] += dy.double().sum(1)[::4]                            # the problems without a bias gradient leave their row alone
+    for name, got, want in (("dW", dw, want_w), ("dB", db, want_b)):
+        err = (got.double() - want).abs()
+        print(f"h2={h2} {name}: max abs error {err.max().item():.3e}, relative to the maximum {err.max().item() / want.abs().max().item():.3e}")
+        if h2:
+            assert err.max().item() / want.abs().max().item() < 3e-6
+        else:
+            torch.testing.assert_close(got.double(), want, rtol=1e-5, atol=2e-6 * M ** 0.5 * 4)
+
+
 @pytest.mark.parametrize("M,N,K", [(1500, 256, 256), (2048, 1024, 256), (1100, 256, 1024), (333, 72, 40), (4096, 288, 256)])
 @pytest.mark.parametrize("mag", [1.0, 1e-7, 3e4])
 def test_gemm_tn_h2_is_fp32_accurate_over_the_exponent_range(M, N, K, mag):

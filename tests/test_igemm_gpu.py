@@ -215,9 +215,9 @@ def test_wgrad_seq_equals_the_single_launches():
 
 
 def test_grouped_tables_are_keyed_by_shape_as_well_as_address():
-    """igemm.transposed / mx8.quantize_grouped cache table staging, offsets and the output size per operand list.  Two weights of different
-    shapes at ONE address (the allocator recycles a freed copy's address for the next layer's) must not share an entry: the second call
-    used to get the first one's buffer size — an out-of-bounds transpose."""
+    """igemm.transposed / mx8.quantize_grouped work out offsets and the output size from the operand list of EACH call.  Two weights of
+    different shapes at ONE address (the allocator recycles a freed copy's address for the next layer's) must each get their own: a cache of
+    these keyed by the bare addresses once gave the second call the first one's buffer size — an out-of-bounds transpose."""
     from partdistillation_amd.functions import igemm, mx8
     buf = (torch.randn(512 * 128, device="cuda") * 2).to(torch.bfloat16)
     w1, w2 = buf[:128 * 128].view(128, 128), buf.view(512, 128)
@@ -228,6 +228,26 @@ def test_grouped_tables_are_keyed_by_shape_as_well_as_address():
         ((q, s),) = mx8.quantize_grouped([w])
         q1, s1 = mx8.quantize(w)
         assert q.shape == w.shape and torch.equal(q, q1) and torch.equal(s, s1)
+
+
+def test_grouped_tables_of_different_lengths_one_after_the_other():
+    """igemm.transposed, declayer.pack and mx8.quantize_grouped with ONE weight and then NINE (the decoder layer's shapes): the staging
+    ring and the device table of the second call are sized for nine problems, whatever the first call used."""
+    from partdistillation_amd.functions import declayer, igemm, mx8
+    g = torch.Generator().manual_seed(9)
+    C, FF = declayer.C, declayer.FF
+    nine = [(torch.randn(n, k, generator=g) * k ** -0.5).to(torch.bfloat16).to(DEV)
+            for n, k in [(C, C), (3 * C, C), (C, C), (FF, C), (C, FF), (C, C), (C, C), (C, C), (C, C)]]
+    single = {tr: [declayer.pack([w], transpose=tr)[0].clone() for w in nine] for tr in (False, True)}
+    for ws in (nine[:1], nine):
+        for w, t in zip(ws, igemm.transposed(ws)):
+            assert t.shape == (w.shape[1], w.shape[0]) and torch.equal(t, w.t())
+        for w, (q, s) in zip(ws, mx8.quantize_grouped(ws)):
+            q1, s1 = mx8.quantize(w)
+            assert q.shape == w.shape and torch.equal(q, q1) and torch.equal(s, s1)
+        for tr in (False, True):
+            for i, p in enumerate(declayer.pack(ws, transpose=tr)):
+                assert torch.equal(p, single[tr][i])
 
 
 @pytest.mark.parametrize("M,K,N,S", [(32768, 256, 768, 256), (2048, 256, 768, 256), (1000, 320, 512, 128), (130, 64, 256, 256)])
