@@ -71,9 +71,13 @@ int pd_gemm_wgrad_f32x3_grouped(const PdGemmWgradDesc *descs, int count, void *t
  * accuracy of an fp32 GEMM at half the matrix work of a three-plane bf16 split.  C[M,N] = A[M,K] B[N,K]^T:
  *   mode 0: + bias;  1: relu(+ bias) and, when bits != NULL, its sign bits (pd_gemm_tn_f16x2_bits_words(M, N) words, the
  *   kernel's accumulator order; N % 256 == 0, M >= 1024);  2: masked by `bits`, colsum[N] += column sums (bits, colsum required).
+ *   The order of the bits is a function of (M, N, K) alone for a given pd_debug_set("f16x2_tile") value: a mode-2 launch reads
+ *   what a mode-1 launch over the same (M, N, K) wrote, with or without row maxima on either side.  Where the row stream carries them (K == 256, N % 256 == 0, N >= 512, M >= 8192) a
+ *   launch with bits brings the maxima of both operands or of neither: one alone is refused (PD_ERR_INVALID_ARG).
  *   a_amax[M] / b_amax[N]: absolute row maxima of A / B (fp32, any value >= the true maximum within a factor 2^7 keeps full
- *   accuracy; NULL = the operand is O(1), no scaling).  c_amax[M] (nullable, ZERO-FILLED by the caller): receives the absolute
- *   row maxima of C (atomic max) — the a_amax of the GEMM that consumes C.
+ *   accuracy; NULL = the operand is O(1), no scaling; the exponent the scale is taken from is clamped, so a row whose maximum is
+ *   2^125 or more leaves fp16's range once scaled and gives inf / NaN results).  c_amax[M] (nullable, ZERO-FILLED by the caller):
+ *   receives the absolute row maxima of C (atomic max) — the a_amax of the GEMM that consumes C.
  * K, lda, ldb multiples of 4, A and B 16-byte aligned.  Reference: the fp32 Linears of the pixel decoder,
  * pixel_decoder/msdeformattn.py:120-135,318 and ops/modules/ms_deform_attn.py:102-130.
  * pd_row_amax_f32: out[r] = max_c |X[r][c]| for operands whose producer does not emit the maxima. */
@@ -102,7 +106,8 @@ int pd_conv3x3_wgrad_nhwc_f16x2(const float *dY, const float *X, float *dWk, flo
  *   0 = 128 x 128 tiles (gemm_tn_f16x2)            3 = register operands (gemm_ra_f16x2_k256, probe build only)
  *   1 = 256 x 256 tiles (gemm_tn_f16x2)            4 = resident accumulators (gemm_kres_f16x2, probe build only)
  *   2 = the row stream (gemm_rows_f16x2_k256)      5 = producer / consumer wavefronts (gemm_kpc_f16x2)
- *  -1 = the launcher refuses the problem (sign bits or forced 256 x 256 tiles where N % 256 != 0 or M < 1024) */
+ *  -1 = the launcher refuses the problem (sign bits or forced 256 x 256 tiles where N % 256 != 0 or M < 1024; sign bits on the row
+ *       stream with the row maxima of one operand only) */
 int pd_gemm_tn_f16x2_which(int M, int N, int K, int lda, int ldb, int mode, int has_bits, int has_a_amax, int has_b_amax, int has_c_amax,
                            int bf16_out);
 

@@ -1032,7 +1032,8 @@ template <int... V, typename F> static void with_constant(int v, std::integer_se
 enum F16x2Family { F16X2_TILE128 = 0, F16X2_TILE256 = 1, F16X2_ROWS = 2, F16X2_RA = 3, F16X2_KRES = 4, F16X2_KPC = 5 };   // the ids of pd_gemm_tn_f16x2_which
 struct F16x2Plan {
   F16x2Family family = F16X2_TILE128;
-  bool refuse = false;       // the launcher returns PD_ERR_INVALID_ARG: sign bits or forced wide tiles on a shape the 256 x 256 kernel does not take
+  bool refuse = false;       // the launcher returns PD_ERR_INVALID_ARG: sign bits or forced wide tiles on a shape the 256 x 256 kernel does not take;
+                             // sign bits on the row stream with the maxima of one operand only
   int nrs = 2, fast = 1;     // tiles: register stages (NRS) and the interleaved interior step (FAST)
   int ntl = 0;               // register operands: 32-column blocks per workgroup (NTL)
   int abl = 0;               // probe build: the ablation bits of the kernel (RABL / KABL)
@@ -1069,10 +1070,12 @@ static F16x2Plan f16x2_plan(int M, int N, int K, int lda, int ldb, int mode, boo
   }
   // N = 1024 <- K = 256 with the ReLU epilogues (the encoder FFN's first Linear and the input gradient of its second: modes 1 / 2 with sign
   // bits): the row stream in its own bit order.  The choice depends on (M, N, K) and the debug value only, so the mode-1 launch that writes a
-  // layer's bits and the mode-2 launch that reads them agree.  DBG_TILED_RELU (and the forced wide tiles) keep the tiled kernel.
+  // layer's bits and the mode-2 launch that reads them agree, whether either of them brings row maxima or not (AM = false: unit scales).
+  // The kernel scales both operands or neither: a bits launch with the maxima of ONE operand is refused, not sent to the tiled kernel and
+  // its other bit order.  DBG_TILED_RELU (and the forced wide tiles) keep the tiled kernel.
   if (dbg != DBG_TILED_RELU && dbg != DBG_WIDE_1 && dbg != DBG_WIDE_2 && dbg != DBG_GUARDED && !bf16_out && (mode == 1 || mode == 2) && has_bits &&
-      K == 256 && panels && N >= 512 && M >= 8192 && has_a_amax && has_b_amax && rows_grid(ncu, p.np) > 0) {
-    p.family = F16X2_ROWS, p.grid = rows_grid(ncu, p.np);
+      K == 256 && panels && N >= 512 && M >= 8192 && rows_grid(ncu, p.np) > 0) {
+    p.family = F16X2_ROWS, p.grid = rows_grid(ncu, p.np), p.refuse = !amax_paired;
     return p;
   }
   // deep K, 256-column panels, plain epilogue, no row maxima out
@@ -1187,8 +1190,10 @@ static int gemm_tn_f16x2_impl(const float *A, const float *B, const float *bias,
     case F16X2_ROWS: {
 #define ROWS(AM, MODE, ...) hipLaunchKernelGGL((gemm_rows_f16x2_k256<AM, MODE>), dim3((unsigned)p.grid), dim3(512), 0, st, A, B, bias, C, M, p.np, lda, ldb, ldc, \
                                                a_amax, b_amax, reinterpret_cast<unsigned *>(c_amax), ##__VA_ARGS__)
-      if (mode == 1) ROWS(true, 1, reinterpret_cast<unsigned short *>(bits), colsum);
-      else if (mode == 2) ROWS(true, 2, reinterpret_cast<unsigned short *>(bits), colsum);
+      if (p.refuse)
+        return pd_set_error(PD_ERR_INVALID_ARG, "pd_gemm_tn_f16x2: sign bits on the row stream (K = 256, N %% 256 == 0, N >= 512, M >= 8192) need the row maxima of both operands or of neither");
+      if (mode == 1) { if (a_amax) ROWS(true, 1, reinterpret_cast<unsigned short *>(bits), colsum); else ROWS(false, 1, reinterpret_cast<unsigned short *>(bits), colsum); }
+      else if (mode == 2) { if (a_amax) ROWS(true, 2, reinterpret_cast<unsigned short *>(bits), colsum); else ROWS(false, 2, reinterpret_cast<unsigned short *>(bits), colsum); }
       else if (a_amax) ROWS(true, 0);
       else ROWS(false, 0);
 #undef ROWS
