@@ -116,7 +116,7 @@ const char *pd_last_error(void);
 
 /* library / ABI version, bumped when a signature, a struct or a PD_* limit changes.  This is the ONE place the number is written:
  * the library returns the macro and the Python binding reads it from here. */
-#define PD_ABI_VERSION 52
+#define PD_ABI_VERSION 53
 int pd_abi_version(void);
 
 /* tools / bench.py only.  For the Mask2Former geometry (3 levels, 4 points, 32 channels, num_query == spatial_size) pd_msda_backward

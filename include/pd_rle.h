@@ -17,6 +17,11 @@
  *                        Three launches: count per (plane, column, segment of PD_RLE_SEG_ROWS rows), exclusive scan in that order,
  *                        boundaries recomputed and written at the scanned offsets.  No atomics, no workgroup waits for another: the table
  *                        is in order and bit-reproducible.
+ *   pd_rle_masked_label_runs   exactly pd_rle_plane_runs(..., binary = 0, ...) of the VIRTUAL planes v[p][y][x] = planes[p][y][x] ?
+ *                        labels[y][x] : 0, with ONE label map uint8 [H, W] (row-major, contiguous) under all planes: "the labels under
+ *                        mask p" (the parts of an object) as run tables without a dense plane per (mask, label) or per
+ *                        mask.  plane_nonzero counts v != 0.  The same three launches (the pixel fetch is a template parameter of the
+ *                        count / write pass), the same workspace query, the same limits.
  *   pd_rle_decode        run starts -> labels int32 [H, W] (row-major), labels[y][x] = sum over the masks i covering the pixel of (i + 1),
  *                        and / or masks uint8 [n, H, W].  Either output may be null, not both.  Every pixel of every output is written
  *                        (n = 0 with labels: zeros).
@@ -44,6 +49,10 @@ int64_t pd_rle_runs_workspace_bytes(int n, int H, int W);
 
 int pd_rle_plane_runs(const uint8_t *planes, int64_t plane_stride, int n, int H, int W, int binary, int capacity, int32_t *run_start,
                       uint8_t *run_value, int32_t *plane_offset, int64_t *plane_nonzero, void *workspace, void *stream);
+
+int pd_rle_masked_label_runs(const uint8_t *planes, int64_t plane_stride, int n, int H, int W, const uint8_t *labels, int capacity,
+                             int32_t *run_start, uint8_t *run_value, int32_t *plane_offset, int64_t *plane_nonzero, void *workspace,
+                             void *stream);
 
 int pd_rle_decode(const int32_t *starts, const int32_t *offsets, int n, int H, int W, int32_t *labels, uint8_t *masks, void *stream);
 

@@ -12,6 +12,8 @@
 //           column totals -> scan over the 64 lanes -> each thread walks its share of one column's segments.  In place.  The workgroups of
 //           xblock 0 also write plane_offset and the plane's non-zero count (int64 sum of wnz).
 //   write   the count pass again, storing (position, value) at the scanned offsets below `capacity`.
+// pd_rle_masked_label_runs is the same three launches with another pixel fetch in the count / write pass: the plane's byte selects
+// between a shared label map's byte and 0.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -31,26 +33,39 @@ __device__ __forceinline__ int wave_sum(int v)
   return v;
 }
 
-template <bool WRITE>
-__global__ __launch_bounds__(64 * PASS_WAVES) void plane_runs_pass(const uint8_t *__restrict__ planes, int64_t plane_stride, int p0, int H, int W,
-                                                                   int nseg, int XB, int SG, int binary, int32_t *__restrict__ cnt,
-                                                                   int32_t *__restrict__ wsum, int32_t *__restrict__ wnz, int capacity,
-                                                                   int32_t *__restrict__ run_start, uint8_t *__restrict__ run_value)
+// the pixel fetch of the count / write pass: plane p's byte at row-major index i, or that of the virtual plane
+// v[p][i] = planes[p][i] ? labels[i] : 0 (one label map under every plane; no such plane is ever written)
+struct PlaneFetch {
+  const uint8_t *__restrict__ planes;
+  int64_t plane_stride;
+  __device__ __forceinline__ int operator()(int p, int i) const { return planes[(int64_t)p * plane_stride + i]; }
+};
+struct MaskedLabelFetch {
+  const uint8_t *__restrict__ planes;
+  int64_t plane_stride;
+  const uint8_t *__restrict__ labels;
+  __device__ __forceinline__ int operator()(int p, int i) const { return planes[(int64_t)p * plane_stride + i] ? labels[i] : 0; }
+};
+
+template <bool WRITE, class Fetch>
+__global__ __launch_bounds__(64 * PASS_WAVES) void plane_runs_pass(const Fetch px, int p0, int H, int W, int nseg, int XB, int SG, int binary,
+                                                                   int32_t *__restrict__ cnt, int32_t *__restrict__ wsum,
+                                                                   int32_t *__restrict__ wnz, int capacity, int32_t *__restrict__ run_start,
+                                                                   uint8_t *__restrict__ run_value)
 {
   const int lane = threadIdx.x & 63;
   const int xb = blockIdx.x / SG, s = (blockIdx.x % SG) * PASS_WAVES + (threadIdx.x >> 6);
   if (s >= nseg) return;                                                      // wave-uniform; the kernel has no barrier
   const int p = p0 + blockIdx.y, x = xb * 64 + lane, y0 = s * SEG;
   const int64_t key = ((int64_t)p * XB + xb) * nseg + s;
-  const uint8_t *pl = planes + (int64_t)p * plane_stride;
   int c = 0, nz = 0;
   if (x < W) {
     int b[SEG];
 #pragma unroll
-    for (int r = 0; r < SEG; ++r) b[r] = pl[min(y0 + r, H - 1) * W + x];      // H * W <= 2^31 - 1: int indices
+    for (int r = 0; r < SEG; ++r) b[r] = px(p, min(y0 + r, H - 1) * W + x);   // H * W <= 2^31 - 1: int indices
     int prev = -1;                                                            // position 0: no pixel before it, a run starts
-    if (y0 > 0) prev = pl[(y0 - 1) * W + x];
-    else if (x > 0) prev = pl[(H - 1) * W + x - 1];
+    if (y0 > 0) prev = px(p, (y0 - 1) * W + x);
+    else if (x > 0) prev = px(p, (H - 1) * W + x - 1);
     if (binary) prev = prev > 0 ? 1 : prev;
     int off = WRITE ? cnt[key * 64 + lane] : 0;
 #pragma unroll
@@ -166,6 +181,37 @@ bool runs_dims(int n, int H, int W, int *nseg, int *XB)
   *XB = (W + 63) / 64;
   return (int64_t)n * *XB * *nseg * 64 <= 0x7fffffffLL;
 }
+// the three launches of pd_rle_plane_runs for either pixel fetch
+template <class Fetch>
+int plane_runs(const char *who, const Fetch &px, bool null_input, int n, int H, int W, int binary, int capacity, int32_t *run_start,
+               uint8_t *run_value, int32_t *plane_offset, int64_t *plane_nonzero, void *workspace, void *stream_)
+{
+  int nseg, XB;
+  if (capacity < 0 || px.plane_stride < 0 || !runs_dims(n, H, W, &nseg, &XB))
+    return pd_set_error(PD_ERR_INVALID_ARG, "%s: bad sizes n=%d H=%d W=%d capacity=%d plane_stride=%lld", who, n, H, W, capacity,
+                        (long long)px.plane_stride);
+  if (!plane_offset || (n > 0 && !plane_nonzero)) return pd_set_error(PD_ERR_INVALID_ARG, "%s: null pointer", who);
+  hipStream_t stream = (hipStream_t)stream_;
+  if (n == 0 || H == 0 || W == 0) {                                            // no pixel, no run
+    if (hipMemsetAsync(plane_offset, 0, sizeof(int32_t) * ((size_t)n + 1), stream) != hipSuccess ||
+        (n > 0 && hipMemsetAsync(plane_nonzero, 0, sizeof(int64_t) * (size_t)n, stream) != hipSuccess))
+      return pd_check_launch(who);
+    return PD_OK;
+  }
+  if (null_input || !workspace || (capacity > 0 && (!run_start || !run_value))) return pd_set_error(PD_ERR_INVALID_ARG, "%s: null pointer", who);
+  const int64_t keys = (int64_t)n * XB * nseg;
+  int32_t *cnt = (int32_t *)workspace, *wsum = cnt + keys * 64, *wnz = wsum + keys;
+  const int SG = (nseg + PASS_WAVES - 1) / PASS_WAVES;
+  for (int p0 = 0; p0 < n; p0 += MAX_GRID_Y)
+    hipLaunchKernelGGL((plane_runs_pass<false, Fetch>), dim3(XB * SG, n - p0 < MAX_GRID_Y ? n - p0 : MAX_GRID_Y), dim3(64 * PASS_WAVES), 0, stream,
+                       px, p0, H, W, nseg, XB, SG, binary, cnt, wsum, wnz, 0, nullptr, nullptr);
+  hipLaunchKernelGGL(plane_runs_scan, dim3(n * XB), dim3(64 * SCAN_PARTS), 0, stream, cnt, wsum, wnz, nseg, XB, n, plane_offset, plane_nonzero);
+  if (capacity > 0)
+    for (int p0 = 0; p0 < n; p0 += MAX_GRID_Y)
+      hipLaunchKernelGGL((plane_runs_pass<true, Fetch>), dim3(XB * SG, n - p0 < MAX_GRID_Y ? n - p0 : MAX_GRID_Y), dim3(64 * PASS_WAVES), 0, stream,
+                         px, p0, H, W, nseg, XB, SG, binary, cnt, wsum, wnz, capacity, run_start, run_value);
+  return pd_check_launch(who);
+}
 }  // namespace
 
 extern "C" int pd_rle_seg_rows(void) { return SEG; }
@@ -178,34 +224,18 @@ extern "C" int64_t pd_rle_runs_workspace_bytes(int n, int H, int W)
 }
 
 extern "C" int pd_rle_plane_runs(const uint8_t *planes, int64_t plane_stride, int n, int H, int W, int binary, int capacity, int32_t *run_start,
-                                 uint8_t *run_value, int32_t *plane_offset, int64_t *plane_nonzero, void *workspace, void *stream_)
+                                 uint8_t *run_value, int32_t *plane_offset, int64_t *plane_nonzero, void *workspace, void *stream)
 {
-  int nseg, XB;
-  if (capacity < 0 || plane_stride < 0 || !runs_dims(n, H, W, &nseg, &XB))
-    return pd_set_error(PD_ERR_INVALID_ARG, "pd_rle_plane_runs: bad sizes n=%d H=%d W=%d capacity=%d plane_stride=%lld", n, H, W, capacity,
-                        (long long)plane_stride);
-  if (!plane_offset || (n > 0 && !plane_nonzero)) return pd_set_error(PD_ERR_INVALID_ARG, "pd_rle_plane_runs: null pointer");
-  hipStream_t stream = (hipStream_t)stream_;
-  if (n == 0 || H == 0 || W == 0) {                                            // no pixel, no run
-    if (hipMemsetAsync(plane_offset, 0, sizeof(int32_t) * ((size_t)n + 1), stream) != hipSuccess ||
-        (n > 0 && hipMemsetAsync(plane_nonzero, 0, sizeof(int64_t) * (size_t)n, stream) != hipSuccess))
-      return pd_check_launch("pd_rle_plane_runs");
-    return PD_OK;
-  }
-  if (!planes || !workspace || (capacity > 0 && (!run_start || !run_value)))
-    return pd_set_error(PD_ERR_INVALID_ARG, "pd_rle_plane_runs: null pointer");
-  const int64_t keys = (int64_t)n * XB * nseg;
-  int32_t *cnt = (int32_t *)workspace, *wsum = cnt + keys * 64, *wnz = wsum + keys;
-  const int SG = (nseg + PASS_WAVES - 1) / PASS_WAVES;
-  for (int p0 = 0; p0 < n; p0 += MAX_GRID_Y)
-    hipLaunchKernelGGL(plane_runs_pass<false>, dim3(XB * SG, n - p0 < MAX_GRID_Y ? n - p0 : MAX_GRID_Y), dim3(64 * PASS_WAVES), 0, stream, planes,
-                       plane_stride, p0, H, W, nseg, XB, SG, binary, cnt, wsum, wnz, 0, nullptr, nullptr);
-  hipLaunchKernelGGL(plane_runs_scan, dim3(n * XB), dim3(64 * SCAN_PARTS), 0, stream, cnt, wsum, wnz, nseg, XB, n, plane_offset, plane_nonzero);
-  if (capacity > 0)
-    for (int p0 = 0; p0 < n; p0 += MAX_GRID_Y)
-      hipLaunchKernelGGL(plane_runs_pass<true>, dim3(XB * SG, n - p0 < MAX_GRID_Y ? n - p0 : MAX_GRID_Y), dim3(64 * PASS_WAVES), 0, stream, planes,
-                         plane_stride, p0, H, W, nseg, XB, SG, binary, cnt, wsum, wnz, capacity, run_start, run_value);
-  return pd_check_launch("pd_rle_plane_runs");
+  return plane_runs("pd_rle_plane_runs", PlaneFetch{planes, plane_stride}, !planes, n, H, W, binary, capacity, run_start, run_value, plane_offset,
+                    plane_nonzero, workspace, stream);
+}
+
+extern "C" int pd_rle_masked_label_runs(const uint8_t *planes, int64_t plane_stride, int n, int H, int W, const uint8_t *labels, int capacity,
+                                        int32_t *run_start, uint8_t *run_value, int32_t *plane_offset, int64_t *plane_nonzero, void *workspace,
+                                        void *stream)
+{
+  return plane_runs("pd_rle_masked_label_runs", MaskedLabelFetch{planes, plane_stride, labels}, !planes || !labels, n, H, W, 0, capacity,
+                    run_start, run_value, plane_offset, plane_nonzero, workspace, stream);
 }
 
 extern "C" int pd_rle_decode(const int32_t *starts, const int32_t *offsets, int n, int H, int W, int32_t *labels, uint8_t *masks, void *stream_)

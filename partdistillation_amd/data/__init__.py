@@ -1,3 +1,4 @@
+from .cityscapes_part_record import cityscapes_part_records, load_object_and_parts  # noqa: F401
 from .device_mapper import DevicePartDistillationMapper, DeviceProposalMapper  # noqa: F401
 from .gt_part_mapper import DeviceCityscapesPartMapper, DeviceGTPartMapper, DeviceVOCPartsMapper  # noqa: F401
 from .part_imagenet_mapper import DevicePartImageNetMapper  # noqa: F401

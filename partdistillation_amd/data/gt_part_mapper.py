@@ -19,6 +19,7 @@ import torch
 from ..compat import BitMasks, Instances
 from ..functions.input_pipeline import nearest_index, resample_coeffs, resample_u8, rle_sample_groups, to_device, upload_image
 from ..utils import rle as _rle
+from .cityscapes_part_record import load_object_and_parts
 from .device_mapper import random_crop, read_image
 
 XYXY_ABS, XYWH_ABS = 0, 1                                                    # detectron2 BoxMode values
@@ -168,6 +169,11 @@ class DeviceGTPartMapper:
             raise NotImplementedError(f"bbox_mode {mode}: only XYXY_ABS (0) and XYWH_ABS (1) boxes are mapped")
         return b
 
+    def from_tuple(self, pair):
+        """the (dict, part_file) records of a PATH_ONLY dataset: CityscapesPartMapper's alone"""
+        raise NotImplementedError(f"{type(self).__name__}: a (dict, part_file) tuple is the input of DeviceCityscapesPartMapper only "
+                                  "(CUSTOM_DATASETS.CITYSCAPES_PART.PATH_ONLY); pass a record with annotations / part_annotations")
+
     def parse(self, dataset_dict):
         """the static part of a record: objects without `iscrowd`, their parts flattened, boxes, classes, segmentations"""
         objs = [(i, o) for i, o in enumerate(dataset_dict["annotations"]) if o.get("iscrowd", 0) == 0]
@@ -200,10 +206,12 @@ class DeviceGTPartMapper:
     def __call__(self, dataset_dict):
         """dataset_dict: {"image": decoded uint8 HWC array (or "file_name" readable by Pillow), "annotations": the objects (RLE
         "segmentation", "bbox" [+ "bbox_mode", XYXY_ABS when absent], "category_id"), "part_annotations": per object a list of parts (RLE
-        "segmentation", the part class, and for the Pascal flavour "bbox"), ...} -> the reference mapper's output dict, on the device"""
+        "segmentation", the part class, and for the Pascal flavour "bbox"), ...} -> the reference mapper's output dict, on the device.
+        A (dict, part_file) tuple goes through `from_tuple` first (the Cityscapes mapper's PATH_ONLY records; None when it has no objects)"""
         if isinstance(dataset_dict, tuple):
-            raise NotImplementedError("the (dict, part_file) input of CityscapesPartMapper reads the part ids with panoptic_parts, which is "
-                                      "not available: pass records whose annotations / part_annotations are already RLE")
+            dataset_dict = self.from_tuple(dataset_dict)
+            if dataset_dict is None:
+                return None
         rec = self.parse(dataset_dict)
         img = upload_image(read_image(dataset_dict), self.device)
         H, W = int(img.shape[0]), int(img.shape[1])
@@ -279,3 +287,18 @@ class DeviceCityscapesPartMapper(DeviceGTPartMapper):
         if is_train:
             return super()._resize_args(cfg, is_train)
         return cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST, "choice"
+
+    def from_tuple(self, pair):
+        """reference :201-211: (record, gtFinePanopticParts.tif path or int32 uid map) -> the record with the objects and parts of
+        `load_object_and_parts` (cityscapes_part_record.py), a copy: the reference writes them into its input; None when the record has no
+        annotation with a segmentation.  The panoptic_parts decoding exists as a device kernel only: a mapper that is not on a GPU
+        refuses the tuple before it looks at the record or the file."""
+        if self.device.type != "cuda":
+            raise NotImplementedError("the (dict, part_file) input of CityscapesPartMapper reads the part ids with panoptic_parts, which is "
+                                      "restated here as a device kernel only (pd_pp_decode_uids): on a mapper that is not on a GPU pass "
+                                      "records whose annotations / part_annotations are already RLE")
+        record, part_file = pair
+        objects, parts = load_object_and_parts(record, part_file, self.device)
+        if objects is None:
+            return None
+        return dict(record, annotations=objects, part_annotations=parts)

@@ -54,12 +54,36 @@ def _planes_u8(planes, who):
     return planes.view(torch.uint8) if planes.dtype == torch.bool else planes
 
 
+def _labels_u8(labels, planes, who):
+    if labels.dim() != 2 or labels.dtype != torch.uint8 or tuple(labels.shape) != tuple(planes.shape[1:]):
+        raise ValueError(f"{who}: labels uint8 {tuple(planes.shape[1:])} expected, got {labels.dtype} {tuple(labels.shape)}")
+    if labels.device != planes.device:
+        raise ValueError(f"{who}: planes on {planes.device}, labels on {labels.device}")
+    return labels.contiguous()
+
+
 def plane_runs(planes, binary):
     """planes uint8 / bool [n, H, W] on the GPU -> host arrays (offsets int32 [n + 1], starts int32, values uint8, nonzero int64 [n]): the
     runs of every plane's COLUMN-major flattening (plane i: entries [offsets[i], offsets[i + 1])), of (byte != 0) when `binary`, of the
     byte values otherwise, and the planes' exact non-zero pixel counts.  Two blocking reads: offsets + counts, then the run table."""
     _require_gpu(planes, "pd_rle_plane_runs")
-    planes = _planes_u8(planes, "plane_runs")
+    return _runs(_planes_u8(planes, "plane_runs"), "plane_runs", "pd_rle_plane_runs", (int(bool(binary)),))
+
+
+def plane_label_runs(planes, labels):
+    """planes uint8 / bool [n, H, W] and labels uint8 [H, W] on the GPU -> `plane_runs(v, binary=False)` of the virtual planes
+    v[i] = where(planes[i], labels, 0), which are never written (pd_rle_masked_label_runs): the same host tuple, the same grow-and-relaunch
+    path, the same two blocking reads"""
+    _require_gpu(planes, "pd_rle_masked_label_runs")
+    _require_gpu(labels, "pd_rle_masked_label_runs")
+    planes = _planes_u8(planes, "plane_label_runs")
+    labels = _labels_u8(labels, planes, "plane_label_runs")
+    return _runs(planes, "plane_label_runs", "pd_rle_masked_label_runs", (labels.data_ptr(),))
+
+
+def _runs(planes, who, entry, extra):
+    """the launch / read / grow / read sequence of `plane_runs` for the entry point `entry`, whose arguments between W and capacity are
+    `extra`"""
     n, H, W = (int(s) for s in planes.shape)
     if n == 0 or H == 0 or W == 0:
         return np.zeros(n + 1, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.uint8), np.zeros(n, dtype=np.int64)
@@ -67,7 +91,7 @@ def plane_runs(planes, binary):
     assert lib.pd_rle_seg_rows() == SEG_ROWS
     work_bytes = lib.pd_rle_runs_workspace_bytes(n, H, W)
     if work_bytes < 0:
-        raise ValueError(f"plane_runs: {n} planes of {H} x {W} are beyond the limits of pd_rle_plane_runs (include/pd_rle.h)")
+        raise ValueError(f"{who}: {n} planes of {H} x {W} are beyond the limits of {entry} (include/pd_rle.h)")
     buf = _buffers.get(dev)
     if buf is None:
         buf = _buffers[dev] = _Buffers(dev)
@@ -78,9 +102,9 @@ def plane_runs(planes, binary):
 
         def launch():
             cap = buf.capacity
-            _lib.check(lib.pd_rle_plane_runs(planes.data_ptr(), stride, n, H, W, int(bool(binary)), cap, buf.runs.data_ptr(),
-                                             buf.runs.data_ptr() + 4 * cap, buf.head.data_ptr() + 8 * n, buf.head.data_ptr(),
-                                             buf.work.data_ptr(), st))
+            _lib.check(getattr(lib, entry)(planes.data_ptr(), stride, n, H, W, *extra, cap, buf.runs.data_ptr(),
+                                           buf.runs.data_ptr() + 4 * cap, buf.head.data_ptr() + 8 * n, buf.head.data_ptr(),
+                                           buf.work.data_ptr(), st))
 
         launch()
         buf.host_head[:12 * n + 4].copy_(buf.head[:12 * n + 4], non_blocking=True)
@@ -123,6 +147,22 @@ def encode_label_map(labels, present=None):
     if present is None:
         present = [int(l) for l in np.flatnonzero(counts[1:]) + 1]
     return _rle.runs_to_coco_json(values, lengths, (H, W), present), counts
+
+
+def encode_plane_labels(planes, labels):
+    """planes uint8 / bool [n, H, W] and labels uint8 [H, W] on the GPU (0 = background) -> (per plane the list [(label, entry), ...] in
+    ascending label order over the non-zero labels that occur under the plane, entry = utils.rle.labels_to_coco_json(where(plane,
+    labels, 0), [label])[0]; pixel counts int64 numpy [n, 256] by plane and label value).  Only run tables cross the bus."""
+    offsets, starts, values, _ = plane_label_runs(planes, labels)
+    n, H, W = (int(s) for s in planes.shape)
+    out, counts = [], np.zeros((n, 256), dtype=np.int64)
+    for i in range(n):
+        a, b = int(offsets[i]), int(offsets[i + 1])
+        lengths = np.diff(starts[a:b].astype(np.int64), append=H * W)
+        counts[i] = label_counts(values[a:b], lengths)
+        present = [int(l) for l in np.flatnonzero(counts[i, 1:]) + 1]
+        out.append(list(zip(present, _rle.runs_to_coco_json(values[a:b], lengths, (H, W), present))))
+    return out, counts
 
 
 def label_counts(values, lengths, minlength=256):
